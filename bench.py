@@ -16,8 +16,9 @@ shape; strong scaling), with vote scores, FedMSE weights and AUCs exchanged
 by RCCL all-reduce and the selected models by an RCCL all-gather over xGMI.
 No x N factor is applied: five trained clients occupy 5 of one GPU's 256 CUs,
 so sharding them can only add exchange latency, and the curve shows that.
-Two further measurements ride along in their own fields, never folded into
-``value``:
+A plain run sets up, warms up, times the steps and prints the line.  With
+``--full`` two further measurements (runs of their own, N > 1 only) ride along
+in their own fields, never folded into ``value``:
   * ``weak_scaling`` – ONE decentralised federation of 10*N clients (10 per
     GPU; the reference's 10/15/20/50-client network-scale configs
     generalised): its rounds/s and AUC;
@@ -35,7 +36,12 @@ architecture — there is no network access for the real dataset.  Compute is
 fp32 end to end (the reference's dtype).  ``vs_baseline`` divides by the
 reference's best measured round rate, 0.30 rounds/s.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+``--dump-outputs DIR`` writes what the last timed round computed (every
+client's model, the per-client AUCs, the selection, the aggregator, the epochs
+run) as ``DIR/<name>.npy``; the inputs are seeded, so two builds run with the
+same arguments can be compared array for array.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
         torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -245,6 +251,40 @@ def _auc(last, fed=None, phantom=False):
     return (float(np.mean(m)), float(np.min(m))) if m.size else (float("nan"), float("nan"))
 
 
+DUMP_LIMIT_BYTES = 48 << 20   # --dump-outputs: parameter rows beyond this are sampled (fixed seed)
+
+
+def _dump_outputs(path: str, fed, comm, last) -> None:
+    """``--dump-outputs DIR``: what the last timed round handed its caller, as
+    ``DIR/<name>.npy`` -- every local client's model parameters after the
+    round (float32 [clients, padded parameters]; a job of several ranks writes
+    one ``client_params_rank<r>.npy`` per rank) and, from rank 0, the round's
+    RoundResult: per-client detection AUC, the selected clients, the elected
+    aggregator (-1: none) and the local epochs each trained client ran
+    (float64).  The data, the initial models and the selections are seeded,
+    so two builds given the same arguments are compared array for array."""
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if comm.world_size == 1 else f"_rank{comm.rank}"
+    params = fed.engine.store.params.detach().to("cpu", torch.float32).numpy()
+    budget = DUMP_LIMIT_BYTES // max(1, comm.world_size)
+    if params.nbytes > budget:
+        keep = max(1, budget // (params.shape[1] * 4))
+        rows = np.sort(np.random.default_rng(0).choice(params.shape[0], size=keep, replace=False))
+        np.save(os.path.join(path, f"client_params_rows{suffix}.npy"), rows.astype(np.float64))
+        params = params[rows]
+    np.save(os.path.join(path, f"client_params{suffix}.npy"), np.ascontiguousarray(params))
+    if not comm.is_root or last is None:
+        return
+    np.save(os.path.join(path, "client_auc.npy"), np.asarray(last.metrics, dtype=np.float64))
+    np.save(os.path.join(path, "selected.npy"), np.asarray(list(last.selected), dtype=np.float64))
+    agg = -1 if last.aggregator is None else int(last.aggregator)
+    np.save(os.path.join(path, "aggregator.npy"), np.asarray([agg], dtype=np.float64))
+    epochs = np.zeros(fed.N, dtype=np.float64)
+    for c, e in (getattr(last, "epochs_run", None) or {}).items():
+        epochs[int(c)] = float(e)
+    np.save(os.path.join(path, "epochs_run.npy"), epochs)
+
+
 def distinct_devices(comm) -> int:
     """Number of distinct physical GPUs the job's ranks run on (the collective
     self-test's device identities; ranks sharing one GPU count once)."""
@@ -333,8 +373,14 @@ def _main(argv, real_stdout: int):
     p.add_argument("--phantom-ranks", type=int, default=0,
                    help="projection on ONE GPU: run rank 0 of a W-rank weak-scaling job (10 clients per rank) "
                         "with the collectives stubbed out (parallel.comm.PhantomComm); labelled as a projection")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run the measurements that take runs of their own: at N > 1 the "
+                        "weak_scaling and independent_federations federations (a plain run times the headline only)")
     p.add_argument("--no-extra", action="store_true",
-                   help="N > 1: skip the weak_scaling and independent_federations measurements")
+                   help="with --full at N > 1: skip the weak_scaling and independent_federations measurements")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed rounds write what the last one computed (client models, AUCs, selection, "
+                        "aggregator, epochs run) as DIR/<name>.npy")
     args = p.parse_args(argv)
     if args.clients is not None and args.clients_per_gpu is not None:
         p.error("--clients and --clients-per-gpu are exclusive")
@@ -393,6 +439,8 @@ def _main(argv, real_stdout: int):
     if time_train:
         fed._fast.train_timing = True
     dt, last, train_ms, epochs_mean = _measure(fed, comm, device, args.steps, args.warmup, args.profile)
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, fed, comm, last)
     fed_rps = args.steps / dt
     auc, auc_min = _auc(last, fed, phantom)
     rec = None
@@ -477,7 +525,7 @@ def _main(argv, real_stdout: int):
             with open(args.out, "w") as f:
                 f.write(line + "\n")
 
-    if n_gpus > 1 and not phantom and not args.no_extra:
+    if args.full and n_gpus > 1 and not phantom and not args.no_extra:
         fed.finish()
         # The headline must not depend on the extras: a rank that raises in
         # them leaves the others blocked in a collective.  Every rank arms a

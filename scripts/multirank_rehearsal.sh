@@ -20,7 +20,7 @@ COMM=${COMM:-gloo}
 CARG=""
 [ "$COMM" = ipc ] && CARG="--comm ipc"
 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $NR --master-addr 127.0.0.1 \
-  --master-port 29517 bench.py --gpus $NR --steps ${STEPS:-20} --warmup 5 $CARG \
+  --master-port 29517 bench.py --gpus $NR --steps ${STEPS:-20} --warmup 5 --full $CARG \
   --out "$OUT/rehearsal_bench${NR}_$COMM.json" > "$OUT/rehearsal_bench$NR.log" 2>&1
 rc=$?
 echo "bench $NR ranks rc=$rc"; tail -n 3 "$OUT/rehearsal_bench$NR.log"

@@ -16,8 +16,6 @@ from fedmse_decentralized_amd.data.scaler import MinMaxScaler, StandardScaler
 from fedmse_decentralized_amd.data.synthetic import SyntheticSpec, generate_client, generate_federation
 from fedmse_decentralized_amd.ops import _host
 
-REF = "/root/reference"
-
 
 def _heavy(n=500, d=20, seed=0):
     rng = np.random.default_rng(seed)
@@ -107,13 +105,13 @@ def test_native_csv_reader_matches_pandas(tmp_path):
     assert np.array_equal(ours, ref)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "Data/N-BaIoT/IID-10-Client_Data/Client-1/normal")),
-                    reason="reference data not mounted")
-def test_native_csv_reader_on_reference_file():
-    d = os.path.join(REF, "Data/N-BaIoT/IID-10-Client_Data/Client-1/normal")
+def test_native_csv_reader_on_reference_file(reference_root):
+    """The first 120 rows of the reference's N-BaIoT IID Client-1 normal CSV,
+    byte for byte as shipped (tests/golden/reference)."""
+    d = os.path.join(reference_root, "Data/N-BaIoT/IID-10-Client_Data/Client-1/normal")
     ours = load_data(d, cache=False)
     ref = pd.read_csv(os.path.join(d, "data.csv"), header=None, float_precision="round_trip").values
-    assert ours.shape == (1691, 115)
+    assert ours.shape == (120, 115)
     assert np.array_equal(ours, ref)
 
 

@@ -40,16 +40,20 @@ def test_prof_summary_on_synthetic_db(tmp_path):
     assert "fedmx::train_kernel<false>" in s and "one round timeline" in s
 
 
-def test_bench_stdout_is_one_json_line():
+def test_bench_stdout_is_one_json_line(tmp_path):
     """The driver contract: `python bench.py ...` prints exactly one JSON line
     on stdout with the BASELINE metric and the required fields (CPU engine,
-    one short round)."""
+    one short round), and `--dump-outputs DIR` leaves the last timed round's
+    results as float32 / float64 arrays."""
     import subprocess
 
+    import numpy as np
+
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--backend", "torch", "--steps", "1",
-                        "--warmup", "0", "--epochs", "1", "--no-artifacts"], cwd=root, capture_output=True,
-                       text=True, timeout=240)
+                        "--warmup", "0", "--epochs", "1", "--no-artifacts", "--dump-outputs", str(dump)],
+                       cwd=root, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -62,6 +66,16 @@ def test_bench_stdout_is_one_json_line():
     assert rec["higher_is_better"] is True and rec["value"] > 0
     for k in ("model", "global_batch", "seq_len", "parallelism"):
         assert k in rec["config"], k
+    assert "weak_scaling" not in rec and "independent_federations" not in rec
+    arrays = {p.name: np.load(p) for p in dump.iterdir()}
+    assert sorted(arrays) == ["aggregator.npy", "client_auc.npy", "client_params.npy", "epochs_run.npy",
+                              "selected.npy"]
+    assert arrays["client_params.npy"].dtype == np.float32 and arrays["client_params.npy"].shape[0] == 10
+    assert np.isfinite(arrays["client_params.npy"]).all()
+    assert all(a.dtype == np.float64 for n, a in arrays.items() if n != "client_params.npy")
+    auc = arrays["client_auc.npy"]
+    assert auc.shape == (10,) and abs(float(auc.mean()) - rec["detection_auc_mean"]) < 1e-6
+    assert arrays["selected.npy"].shape == (5,) and (arrays["epochs_run.npy"] > 0).sum() == 5
 
 
 def test_partition_devices_pipeline(tmp_path):
@@ -143,8 +157,8 @@ def test_bench_gpus_flag_spawns_ranks_without_a_launcher():
     BASELINE-shaped line (VERDICT r3 Next #1): ``value`` is the 10-client
     federation's rounds/s over the 8 ranks (no x N factor), with the
     10N-client weak-scaling federation and N independent one-GPU
-    federations as separate fields."""
-    rec = _bench_no_launcher(8)
+    federations as separate fields of a ``--full`` run."""
+    rec = _bench_no_launcher(8, "--full")
     assert rec["n_gpus"] == 8 and rec["config"]["clients"] == 10 and rec["scaling"] == "strong"
     assert rec["value"] == rec["federation_rounds_per_sec"] > 0
     assert "x2" not in rec["unit"] and "10-client federation" in rec["unit"]
@@ -299,7 +313,8 @@ def test_bench_extras_watchdog_prints_the_headline(monkeypatch):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
                         "--gpus", "2", "--backend", "torch", "--steps", "1", "--warmup", "0", "--epochs", "1",
-                        "--no-artifacts"], cwd=root, capture_output=True, text=True, timeout=400, env=env)
+                        "--no-artifacts", "--full"], cwd=root, capture_output=True, text=True, timeout=400,
+                       env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
