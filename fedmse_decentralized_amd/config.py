@@ -80,6 +80,10 @@ class ExperimentConfig:
     malicious_clients: List[int] = field(default_factory=list)  # fault injection (tests)
     malicious_scale: float = 10.0
     dropped_clients: List[int] = field(default_factory=list)    # fault injection: never vote / aggregate
+    # update type "trimmed_mean": per coordinate, the floor(ratio * k) lowest and
+    # as many highest of the k selected models' values are dropped before the
+    # mean (at most (k - 1) // 2 per side; protocol/aggregation.py trim_count)
+    robust_trim_ratio: float = 0.2
     # --- protocol variants ---------------------------------------------------
     # "first_voter": the reference's decentralised election (first selected
     #   voter that finds an eligible candidate decides, client_trainer.py:249-285);
@@ -191,6 +195,13 @@ def _str2bool(s):
     return s.lower() in ("1", "true", "yes", "y", "on")
 
 
+_HELP = {
+    "update_types": "any of: avg fedprox mse_avg fusion_avg trimmed_mean median",
+    "robust_trim_ratio": "trimmed_mean: fraction of the selected models dropped at each end of every "
+                         "coordinate's order (default 0.2)",
+}
+
+
 def add_arguments(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     d = ExperimentConfig()
     for f in dataclasses.fields(ExperimentConfig):
@@ -200,11 +211,11 @@ def add_arguments(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
             p.add_argument(name, type=_str2bool, default=None, metavar="BOOL")
         elif isinstance(default, list):
             elem = int if f.name in ("malicious_clients", "dropped_clients") else str
-            p.add_argument(name, type=elem, nargs="*", default=None)
+            p.add_argument(name, type=elem, nargs="*", default=None, help=_HELP.get(f.name))
         elif isinstance(default, int) and not isinstance(default, bool):
             p.add_argument(name, type=int, default=None)
         elif isinstance(default, float):
-            p.add_argument(name, type=float, default=None)
+            p.add_argument(name, type=float, default=None, help=_HELP.get(f.name))
         elif default is None and str(f.type) in ("Optional[float]", "float"):   # e.g. synthetic_alpha
             p.add_argument(name, type=float, default=None)
         elif default is None and str(f.type) in ("Optional[int]", "int"):

@@ -208,6 +208,12 @@ class Engine:
     def weighted_sum(self, stack: torch.Tensor, weights: Sequence[float]) -> torch.Tensor:
         raise NotImplementedError
 
+    def robust_aggregate(self, stack: torch.Tensor, t: int) -> torch.Tensor:
+        """[k, P] -> [P]: per coordinate, the mean of the values ranked
+        t .. k-t-1 (total order with ties by row; ``protocol/aggregation.py``),
+        added in row order."""
+        raise NotImplementedError
+
     def param_drift(self, hist: torch.Tensor, new: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
 

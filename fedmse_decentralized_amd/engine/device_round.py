@@ -15,6 +15,8 @@ can be *enqueued* instead:
     [ONE all-gather (RCCL, or --comm ipc): the selected models + their vote records]
     elect_wsum_kernel       aggregator (first voter / majority, thesis cap and
                             fallback), FedAvg / FedMSE / sample weights, aggregate
+    [robust_agg_kernel      trimmed_mean / median only: per-coordinate order statistic
+                            over the same rows, overwrites the aggregate]
     verify_decide_kernel    fused: forward(agg, every hosted client's verification
                             data) [+ own model: thesis], MSE + drift reductions,
                             ModelVerifier / thesis rule (or centralised push),
@@ -53,6 +55,7 @@ import torch
 
 from ..models.layout import P_PAD
 from ..ops import _hip
+from ..protocol.aggregation import ROBUST_TYPES, trim_count
 
 # fence-less device events for the kernel-to-kernel stream dependencies
 # ("0": torch events, which record with a system-scope fence)
@@ -88,8 +91,8 @@ def fast_path_supported(fed) -> Optional[str]:
         (cfg.aggregation_mode in ("decentralized", "centralized"), f"aggregation mode {cfg.aggregation_mode}"),
         (cfg.protocol_variant == "code" or _thesis_fused_ok(fed),
          "thesis variant with verification rows beyond the fused kernel's LDS buffer"),
-        (fed.update_type in ("avg", "fedprox", "mse_avg", "fusion_avg"), f"update type {fed.update_type}"),
-        (cfg.metric in ("AUC", "classification", "time"), f"metric {cfg.metric}"),
+        (fed.update_type in ("avg", "fedprox", "mse_avg", "fusion_avg", "trimmed_mean", "median"),
+         f"update type {fed.update_type}"),        (cfg.metric in ("AUC", "classification", "time"), f"metric {cfg.metric}"),
         # dropped clients leave at least one selection per round (k >= 1: the
         # election kernel needs a voter); larger drop sets take the host path
         (len({c for c in cfg.dropped_clients if 0 <= c < fed.N}) < max(1, int(cfg.num_participants * fed.N)),
@@ -265,8 +268,11 @@ class DeviceRound:
         # 2 = sample-weighted FedAvg (host-computed: they depend on the selection only)
         # fusion_avg: weights formed on the device each round (rule 2 reads them
         # from self.fw; Federation._fusion_weights_t, the host path's computation)
+        # trimmed_mean / median: rule 0, then robust_agg_kernel overwrites the aggregate
         self.fusion = fed.update_type == "fusion_avg"
-        self.rule = 1 if fed.update_type == "mse_avg" else (2 if cfg.fedavg_sample_weighted or self.fusion else 0)
+        self.robust = fed.update_type in ROBUST_TYPES
+        self.rule = 1 if fed.update_type == "mse_avg" else (
+            2 if (cfg.fedavg_sample_weighted or self.fusion) and not self.robust else 0)
         if self.fusion:
             self.fstack = torch.zeros(max(N, 1), P_PAD, dtype=f32, device=dev)
             self.fw = torch.zeros(max(N, 1), dtype=f32, device=dev)
@@ -574,6 +580,12 @@ class DeviceRound:
             w = _hip.WsumArgs(base=base.data_ptr(), rows=rows_ptr, weights=self.weights.data_ptr(),
                               state=self.state.data_ptr(), out=self.agg.data_ptr(), k=k, P=P_PAD)
             _hip.elect_wsum(a, w, dev)
+            if self.robust:
+                # trimmed mean / median: the order-statistic kernel over the same
+                # rows and election state overwrites the plain mean (one extra
+                # launch, paid by these two rules only)
+                _hip.robust_aggregate(base, rows_ptr, k, trim_count(fed.update_type, k, cfg.robust_trim_ratio),
+                                      self.agg, state_ptr=self.state.data_ptr())
             rec["report"] = rep_view
         # the previous round's side work has read the snapshot / report buffers
         side = self.side_slots[rnd % len(self.side_slots)]

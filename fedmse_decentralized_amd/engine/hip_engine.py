@@ -17,6 +17,7 @@
                        hosted client) + ``fedmx_cen_score`` + ``fedmx_auc``
                        -- src/Evaluator/evaluator.py:56-94
 * ``weighted_sum``  -> ``fedmx_weighted_sum`` -- src/Trainer/client_trainer.py:107-130
+* ``robust_aggregate`` -> ``fedmx_robust_agg`` (trimmed mean / median; not in the reference)
 
 Descriptor arrays are cached on the device for static work and streamed
 through a pinned ring otherwise; device->host traffic goes through a pinned
@@ -101,6 +102,9 @@ class HipEngine(Engine):
 
     def weighted_sum(self, stack, weights):
         return _hip.weighted_sum(stack, weights)
+
+    def robust_aggregate(self, stack, t):
+        return _hip.robust_aggregate_stack(stack, int(t))
 
     def param_drift(self, hist, new):
         return _hip.param_drift(hist, new, self._seg)

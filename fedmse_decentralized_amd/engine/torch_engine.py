@@ -146,6 +146,29 @@ class TorchEngine(Engine):
             out = out + stack[k] * w[k]
         return out
 
+    def robust_aggregate(self, stack, t):
+        k, P = stack.shape
+        t = int(t)
+        if k < 1 or t < 0 or 2 * t >= k:
+            raise ValueError(f"robust_aggregate: trim count {t} leaves no model of {k}")
+        st = stack.contiguous().to(torch.float32)
+        # 32-bit keys (held in int64) whose order is -inf < ... < -0 < +0 < ... < +inf < NaN
+        b = st.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        key = torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b | 0x80000000)
+        key = key.masked_fill((b & 0x7FFFFFFF) > 0x7F800000, 0xFFFFFFFF)
+        # rank = position in the stable argsort (ties by row)
+        order = torch.argsort(key, dim=0, stable=True)
+        rank = torch.empty_like(order)
+        rank.scatter_(0, order, torch.arange(k, device=st.device).unsqueeze(1).expand(k, P))
+        kept = (rank >= t) & (rank < k - t)
+        # the kept values in row order, one fp32 rounding per add, from the first kept value
+        acc = torch.zeros(P, dtype=torch.float32, device=st.device)
+        started = torch.zeros(P, dtype=torch.bool, device=st.device)
+        for j in range(k):
+            acc = torch.where(kept[j], torch.where(started, acc + st[j], st[j]), acc)
+            started = started | kept[j]
+        return acc / torch.tensor(float(k - 2 * t), dtype=torch.float32, device=st.device)
+
     def param_drift(self, hist, new):
         a = padded_to_canonical(hist, self.dims)
         b = padded_to_canonical(new.unsqueeze(0), self.dims)

@@ -41,7 +41,7 @@ from .models.layout import P_PAD, ModelDims
 from .models.reference import init_client_params
 from .parallel.comm import Comm, LoopbackComm
 from .parallel.sharding import ShardMap
-from .protocol.aggregation import make_plan
+from .protocol.aggregation import ROBUST_TYPES, make_plan, trim_count
 from .protocol.early_stop import GlobalEarlyStop
 from .protocol.election import OneDraw, elect_aggregator, elect_majority, select_clients
 from .protocol.verification import ThesisVerifier, Verifier, VerifierState
@@ -436,6 +436,7 @@ class Federation:
         if aggregator is not None:
             if info:
                 log.info(f"Client {aggregator + 1} selected as aggregator")
+            robust = self.update_type in ROBUST_TYPES
             with self.tel.phase("aggregate"):
                 if self.update_type == "mse_avg" and cfg.compat == "reference":
                     for _ in selected:          # calculate_mse_score per client (weights unused, Q3)
@@ -447,12 +448,17 @@ class Federation:
                     else:
                         sim = self._fusion_similarity(selected)
                 ns = {c: self.clients[c].train.shape[0] for c in selected} if cfg.fedavg_sample_weighted else None
-                plan = make_plan(self.update_type, selected, aggregator, dev_mse, cfg.compat, sim=sim,
-                                 num_samples=ns, fusion_w=fw)
+                # (the robust rules are no (source, weight) plan: an order statistic per coordinate)
+                plan = None if robust else make_plan(self.update_type, selected, aggregator, dev_mse, cfg.compat,
+                                                     sim=sim, num_samples=ns, fusion_w=fw)
             with self.tel.phase("comm"):
-                stack = self._gather_params([c for c, _ in plan], selected)
+                stack = self._gather_params(list(selected) if robust else [c for c, _ in plan], selected)
             with self.tel.phase("aggregate"):
-                agg = eng.weighted_sum(stack, [w for _, w in plan])
+                if robust:
+                    agg = eng.robust_aggregate(stack, trim_count(self.update_type, len(selected),
+                                                                 cfg.robust_trim_ratio))
+                else:
+                    agg = eng.weighted_sum(stack, [w for _, w in plan])
                 self.agg_counts[aggregator] += 1
                 if self._mine(aggregator):
                     eng.adopt([self._loc(aggregator)], agg, anchor=False)

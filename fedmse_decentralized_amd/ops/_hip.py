@@ -110,6 +110,7 @@ class DecideArgs(ctypes.Structure):
 
 
 VERIFY_MAX_ROWS = 4096   # rows of one receiver's verification data the fused kernel keeps in LDS
+ROBUST_MAX_K = 1024      # models one robust_agg_kernel tile ranks (elect_wsum's row table has the same bound)
 
 IPC_MAX_WORLD = 16
 IPC_MAX_CHUNKS = 64
@@ -161,6 +162,8 @@ def lib():
             sig = {
                 "fedmx_forward_rows": [vp, i32, vp],
                 "fedmx_weighted_sum": [vp, vp, i32, i32, vp, vp],
+                "fedmx_robust_agg": [vp, vp, vp, vp, i32, i32, i32, vp],
+                "fedmx_robust_max_k": [],
                 "fedmx_param_drift": [vp, i32, vp, vp, vp, vp],
                 "fedmx_standardize_lds": [vp, i32, i32, vp, vp],
                 "fedmx_cen_score": [vp, i32, vp],
@@ -206,6 +209,7 @@ def lib():
             assert L.fedmx_ipc_args_size() == ctypes.sizeof(IpcArgs)
             assert L.fedmx_verify_split_args_size() == ctypes.sizeof(VerifySplitArgs)
             assert L.fedmx_ipc_max_world() == IPC_MAX_WORLD and L.fedmx_ipc_max_chunks() == IPC_MAX_CHUNKS
+            assert L.fedmx_robust_max_k() == ROBUST_MAX_K
             _lib = L
     return _lib
 
@@ -718,6 +722,39 @@ def weighted_sum(stack: torch.Tensor, weights: Sequence[float], out: Optional[to
     st = stack.contiguous()
     _check(lib().fedmx_weighted_sum(st.data_ptr(), wptr, K, P, out.data_ptr(), rt.stream), "fedmx_weighted_sum")
     return out
+
+
+def robust_aggregate(base: torch.Tensor, rows_ptr: Optional[int], k: int, t: int, out: torch.Tensor,
+                     state_ptr: int = 0) -> torch.Tensor:
+    """``out[i]`` = trimmed mean (``t`` models trimmed at each end of the
+    per-coordinate order, ties by position; ``t = (k - 1) // 2``: the median)
+    of ``base[rows[j], i]``, j < k, summed in row-table order
+    (fedmx_robust.hip).  ``rows_ptr``: device-visible ``int64[k]`` (e.g. in the
+    mapped descriptor ring), or None for rows 0..k-1.  With ``state_ptr`` the
+    launch writes nothing when the int32 there is negative (no aggregator
+    elected).  Raises ValueError for k or t out of range; nothing is launched."""
+    if base.dim() != 2 or base.dtype != torch.float32 or not base.is_contiguous():
+        raise ValueError("robust_aggregate: base must be a contiguous float32 [rows, P] tensor")
+    P = int(base.shape[1])
+    if not 1 <= k <= ROBUST_MAX_K:
+        raise ValueError(f"robust_aggregate: k = {k} models (1..{ROBUST_MAX_K} supported)")
+    if t < 0 or 2 * t >= k:
+        raise ValueError(f"robust_aggregate: trim count {t} leaves no model of {k}")
+    if rows_ptr is None and k > base.shape[0]:
+        raise ValueError(f"robust_aggregate: k = {k} exceeds the stack's {base.shape[0]} rows")
+    if out.dtype != torch.float32 or out.numel() != P or not out.is_contiguous() or out.device != base.device:
+        raise ValueError("robust_aggregate: out must be a contiguous float32 [P] tensor on base's device")
+    _check(lib().fedmx_robust_agg(base.data_ptr(), rows_ptr or 0, state_ptr, out.data_ptr(), k, P, t,
+                                  _stream(base.device)), "fedmx_robust_agg")
+    return out
+
+
+def robust_aggregate_stack(stack: torch.Tensor, t: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``robust_aggregate`` over a ``[k, P]`` stack in row order."""
+    st = stack.contiguous()
+    if out is None:
+        out = torch.empty(st.shape[1], dtype=torch.float32, device=st.device)
+    return robust_aggregate(st, None, int(st.shape[0]), t, out)
 
 
 def param_drift(hist: torch.Tensor, new: torch.Tensor, seg: torch.Tensor, to_host: bool = False):

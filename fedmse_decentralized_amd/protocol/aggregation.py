@@ -72,7 +72,34 @@ def plan_fusion(selected: Sequence[int], sim: Dict[int, float] = None, weights: 
     return [(cid, float(x)) for cid, x in zip(selected, w)]
 
 
-UPDATE_TYPES = ("avg", "fedprox", "mse_avg", "fusion_avg")
+UPDATE_TYPES = ("avg", "fedprox", "mse_avg", "fusion_avg", "trimmed_mean", "median")
+
+# Robust rules: a per-coordinate order-statistic selection over the selected
+# models, which no (source, weight) plan expresses.  For every coordinate the
+# k values are ranked under the total order -inf < ... < -0 < +0 < ... < +inf
+# < NaN (ties by selection position), the ``t`` lowest and ``t`` highest are
+# dropped, and the rest are added in selection order (fp32, one rounding per
+# add) and divided by ``k - 2t`` (``Engine.robust_aggregate``).  The result
+# depends only on the gathered models and their order, so every rank computes
+# the same bits.  Local training is plain (mu = 0), as for ``avg``.
+ROBUST_TYPES = ("trimmed_mean", "median")
+
+
+def trim_count(update_type: str, k: int, ratio: float = 0.2) -> int:
+    """Models dropped at EACH end of every coordinate's order.
+    ``trimmed_mean``: ``floor(ratio * k)``, at most ``(k - 1) // 2`` (at least
+    one model is always kept); ``median``: ``(k - 1) // 2`` (the middle value
+    for odd k, the mean of the two middle values for even k)."""
+    if k < 1:
+        raise ValueError(f"trim_count: k = {k}")
+    half = (k - 1) // 2
+    if update_type == "median":
+        return half
+    if update_type == "trimmed_mean":
+        if not 0.0 <= ratio < 0.5:
+            raise ValueError(f"robust_trim_ratio must be in [0, 0.5), got {ratio}")
+        return min(int(ratio * k), half)
+    raise ValueError(f"Not a robust update type: {update_type}")
 
 
 def make_plan(update_type: str, selected: Sequence[int], aggregator: int, dev_mse: Dict[int, float] = None,

@@ -110,6 +110,19 @@ def main():
     stack = eng.store.params[:5].contiguous()
     out["weighted_sum_us"] = timeit(lambda: eng.weighted_sum(stack, [0.2] * 5))[0]
     out["param_drift_us"] = timeit(lambda: eng.param_drift(stack[:2], stack[3]))[0]
+    # robust aggregation (trimmed_mean at the default ratio; fedmx_robust.hip), the
+    # extra launch a trimmed_mean / median round pays behind elect_wsum, next to
+    # the plain weighted sum over the same rows: k = 5 (the flagship round) and
+    # k = 40 (the 8-rank job's selection)
+    from fedmse_decentralized_amd.protocol.aggregation import trim_count  # noqa: E402
+
+    agg_out = torch.empty(stack.shape[1], dtype=torch.float32, device=dev)
+    for kk in (5, 40):
+        st = eng.store.params[torch.arange(kk, device=dev) % args.clients].contiguous()
+        t = trim_count("trimmed_mean", kk, 0.2)
+        out[f"weighted_sum_k{kk}_us"] = timeit(lambda: _hip.weighted_sum(st, [1.0 / kk] * kk, out=agg_out))[0]
+        out[f"robust_agg_k{kk}_us"] = timeit(lambda: _hip.robust_aggregate_stack(st, t, out=agg_out))[0]
+        out[f"robust_median_k{kk}_us"] = timeit(lambda: _hip.robust_aggregate_stack(st, (kk - 1) // 2, out=agg_out))[0]
     t0 = time.perf_counter()
     for _ in range(20):
         evaluate_clients(eng, allc, "hybrid", "AUC")
