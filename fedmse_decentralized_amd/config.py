@@ -82,7 +82,9 @@ class ExperimentConfig:
     dropped_clients: List[int] = field(default_factory=list)    # fault injection: never vote / aggregate
     # update type "trimmed_mean": per coordinate, the floor(ratio * k) lowest and
     # as many highest of the k selected models' values are dropped before the
-    # mean (at most (k - 1) // 2 per side; protocol/aggregation.py trim_count)
+    # mean (at most (k - 1) // 2 per side; protocol/aggregation.py trim_count).
+    # "krum" / "multi_krum": the share of the selected models assumed poisoned,
+    # f = floor(ratio * k), at most (k - 3) // 2 (krum_counts)
     robust_trim_ratio: float = 0.2
     # --- protocol variants ---------------------------------------------------
     # "first_voter": the reference's decentralised election (first selected
@@ -196,9 +198,10 @@ def _str2bool(s):
 
 
 _HELP = {
-    "update_types": "any of: avg fedprox mse_avg fusion_avg trimmed_mean median",
-    "robust_trim_ratio": "trimmed_mean: fraction of the selected models dropped at each end of every "
-                         "coordinate's order (default 0.2)",
+    "update_types": "any of: avg fedprox mse_avg fusion_avg trimmed_mean median krum multi_krum",
+    "robust_trim_ratio": "share of the selected models assumed poisoned, in [0, 0.5): trimmed_mean drops that "
+                         "fraction at each end of every coordinate's order, krum / multi_krum discard that "
+                         "fraction of whole models by distance (default 0.2)",
 }
 
 

@@ -214,6 +214,13 @@ class Engine:
         added in row order."""
         raise NotImplementedError
 
+    def krum_aggregate(self, stack: torch.Tensor, f: int, m: int):
+        """[k, P] -> ([P], kept row positions in ascending order): the mean of
+        the ``m`` rows with the lowest Krum scores (sum of a row's
+        ``max(k - f - 2, 0)`` smallest chunk-ordered f64 squared distances;
+        ``protocol/aggregation.py``), added in row order."""
+        raise NotImplementedError
+
     def param_drift(self, hist: torch.Tensor, new: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
 

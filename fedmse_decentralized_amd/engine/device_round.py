@@ -17,6 +17,10 @@ can be *enqueued* instead:
                             fallback), FedAvg / FedMSE / sample weights, aggregate
     [robust_agg_kernel      trimmed_mean / median only: per-coordinate order statistic
                             over the same rows, overwrites the aggregate]
+    [krum_dist / krum_score / krum_mean kernels
+                            krum / multi_krum only: pairwise distances, scores, the
+                            kept rows' mean over the same rows; overwrites the
+                            aggregate, kept mask into a mapped slot]
     verify_decide_kernel    fused: forward(agg, every hosted client's verification
                             data) [+ own model: thesis], MSE + drift reductions,
                             ModelVerifier / thesis rule (or centralised push),
@@ -55,7 +59,7 @@ import torch
 
 from ..models.layout import P_PAD
 from ..ops import _hip
-from ..protocol.aggregation import ROBUST_TYPES, trim_count
+from ..protocol.aggregation import KRUM_TYPES, ROBUST_TYPES, krum_counts, trim_count
 
 # fence-less device events for the kernel-to-kernel stream dependencies
 # ("0": torch events, which record with a system-scope fence)
@@ -91,7 +95,8 @@ def fast_path_supported(fed) -> Optional[str]:
         (cfg.aggregation_mode in ("decentralized", "centralized"), f"aggregation mode {cfg.aggregation_mode}"),
         (cfg.protocol_variant == "code" or _thesis_fused_ok(fed),
          "thesis variant with verification rows beyond the fused kernel's LDS buffer"),
-        (fed.update_type in ("avg", "fedprox", "mse_avg", "fusion_avg", "trimmed_mean", "median"),
+        (fed.update_type in ("avg", "fedprox", "mse_avg", "fusion_avg", "trimmed_mean", "median", "krum",
+                             "multi_krum"),
          f"update type {fed.update_type}"),        (cfg.metric in ("AUC", "classification", "time"), f"metric {cfg.metric}"),
         # dropped clients leave at least one selection per round (k >= 1: the
         # election kernel needs a voter); larger drop sets take the host path
@@ -125,6 +130,7 @@ class LazyRoundResult:
     verification = property(lambda self: self._get("verification"))
     epochs_run = property(lambda self: self._get("epochs_run"))
     stop = property(lambda self: self._get("stop"))
+    agg_kept = property(lambda self: self._get("agg_kept"))
 
 
 class DeviceRound:
@@ -270,9 +276,15 @@ class DeviceRound:
         # from self.fw; Federation._fusion_weights_t, the host path's computation)
         # trimmed_mean / median: rule 0, then robust_agg_kernel overwrites the aggregate
         self.fusion = fed.update_type == "fusion_avg"
+        # krum / multi_krum: rule 0, then the three krum kernels overwrite the aggregate
         self.robust = fed.update_type in ROBUST_TYPES
+        self.krum = fed.update_type in KRUM_TYPES
         self.rule = 1 if fed.update_type == "mse_avg" else (
-            2 if (cfg.fedavg_sample_weighted or self.fusion) and not self.robust else 0)
+            2 if (cfg.fedavg_sample_weighted or self.fusion) and not (self.robust or self.krum) else 0)
+        if self.krum:
+            # one workspace (distances, scores, kept positions), sized once for
+            # the largest selection a round can make (k <= N)
+            self.krum_ws = torch.empty(_hip.krum_workspace_size(max(N, 1)), dtype=torch.float64, device=dev)
         if self.fusion:
             self.fstack = torch.zeros(max(N, 1), P_PAD, dtype=f32, device=dev)
             self.fw = torch.zeros(max(N, 1), dtype=f32, device=dev)
@@ -586,6 +598,17 @@ class DeviceRound:
                 # launch, paid by these two rules only)
                 _hip.robust_aggregate(base, rows_ptr, k, trim_count(fed.update_type, k, cfg.robust_trim_ratio),
                                       self.agg, state_ptr=self.state.data_ptr())
+            elif self.krum:
+                # krum / multi_krum: distances, scores, then the kept rows' mean
+                # over the same rows and election state overwrites the plain
+                # mean (three extra launches, paid by these two rules only);
+                # the kept mask lands in a mapped slot read with the round's report
+                kf, _, km = krum_counts(fed.update_type, k, cfg.robust_trim_ratio)
+                kept_ptr, kept_view = self.rt.out.take(np.int32, k)
+                kept_view[:] = -1
+                _hip.krum_aggregate(base, rows_ptr, k, kf, km, self.agg, state_ptr=self.state.data_ptr(),
+                                    workspace=self.krum_ws, kept_out=kept_ptr)
+                rec["kept"] = kept_view
             rec["report"] = rep_view
         # the previous round's side work has read the snapshot / report buffers
         side = self.side_slots[rnd % len(self.side_slots)]
@@ -757,6 +780,11 @@ class DeviceRound:
                     [fed.save_dirs[c] for c in sel], self.snap_views[si].numpy(), [self._loc(c) for c in sel],
                     [bool(res.best_epoch[i] >= 0) for i in range(len(sel))],
                     [list(res.tracking[i]) for i in range(len(sel))])
+        agg_kept = None
+        if aggregator is not None and "kept" in rec:
+            agg_kept = [c for c, kj in zip(rec["selected"], rec["kept"]) if int(kj) == 1]
+            log.info(f"Aggregate keeps clients {[c + 1 for c in agg_kept]} of {[c + 1 for c in rec['selected']]} "
+                     f"({fed.update_type})")
         verification = []
         if aggregator is not None and self.centralized:
             # centralised push: every client adopted the aggregate, nothing to report
@@ -802,7 +830,7 @@ class DeviceRound:
 
             stop = fed.early.update(metric_stats(metrics)[1])
         rec.update(aggregator=aggregator, metrics=metrics, verification=verification, epochs_run=epochs_local,
-                   stop=stop, done=True)
-        for key in ("handle", "snap_slot", "slot", "report", "_keep", "event", "eval_params", "eval_timing", "train_ev"):
+                   stop=stop, agg_kept=agg_kept, done=True)
+        for key in ("handle", "snap_slot", "slot", "report", "kept", "_keep", "event", "eval_params", "eval_timing", "train_ev"):
             rec.pop(key, None)
         self.all_rounds.pop(rnd, None)

@@ -18,6 +18,7 @@
                        -- src/Evaluator/evaluator.py:56-94
 * ``weighted_sum``  -> ``fedmx_weighted_sum`` -- src/Trainer/client_trainer.py:107-130
 * ``robust_aggregate`` -> ``fedmx_robust_agg`` (trimmed mean / median; not in the reference)
+* ``krum_aggregate`` -> ``fedmx_krum_agg`` (Krum / Multi-Krum; not in the reference)
 
 Descriptor arrays are cached on the device for static work and streamed
 through a pinned ring otherwise; device->host traffic goes through a pinned
@@ -105,6 +106,11 @@ class HipEngine(Engine):
 
     def robust_aggregate(self, stack, t):
         return _hip.robust_aggregate_stack(stack, int(t))
+
+    def krum_aggregate(self, stack, f, m):
+        kept = torch.empty(int(stack.shape[0]), dtype=torch.int32, device=stack.device)
+        agg = _hip.krum_aggregate_stack(stack, int(f), int(m), kept_out=kept)
+        return agg, [int(i) for i in torch.nonzero(kept).flatten().tolist()]
 
     def param_drift(self, hist, new):
         return _hip.param_drift(hist, new, self._seg)

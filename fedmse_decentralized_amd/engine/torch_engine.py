@@ -169,6 +169,51 @@ class TorchEngine(Engine):
             started = started | kept[j]
         return acc / torch.tensor(float(k - 2 * t), dtype=torch.float32, device=st.device)
 
+    def krum_aggregate(self, stack, f, m):
+        k, P = stack.shape
+        f, m = int(f), int(m)
+        if k < 1 or f < 0 or not 1 <= m <= k:
+            raise ValueError(f"krum_aggregate: f = {f}, m = {m} of {k} models")
+        q = max(k - f - 2, 0)
+        st = stack.contiguous().to(torch.float32)
+        dev = st.device
+        # distances: lane l of 256 adds its coordinates l, l + 256, ... in that
+        # order in f64 (the rows zero-extended), then eight folds
+        C = -(-P // 256)
+        pad = torch.zeros(k, C * 256, dtype=torch.float32, device=dev)
+        pad[:, :P] = st
+        p = torch.zeros(k, k, 256, dtype=torch.float64, device=dev)
+        for c in range(C):
+            x = pad[:, c * 256:(c + 1) * 256]
+            e = (x.unsqueeze(1) - x.unsqueeze(0)).to(torch.float64)   # one fp32 rounding, then exact in f64
+            p = p + e * e
+        h = 128
+        while h >= 1:
+            p = p[..., :h] + p[..., h:2 * h]
+            h //= 2
+        D = p[..., 0]
+        D = torch.where(torch.isnan(D), torch.full_like(D, float("inf")), D)
+        # scores: the q smallest of each row's k - 1 distances (non-negative
+        # doubles order as integers; ties by column), added in column order
+        key = D.contiguous().view(torch.int64).clone()
+        key.fill_diagonal_(torch.iinfo(torch.int64).max)
+        ar = torch.arange(k, device=dev)
+        order = torch.argsort(key, dim=1, stable=True)
+        rank = torch.empty_like(order)
+        rank.scatter_(1, order, ar.unsqueeze(0).expand(k, k).contiguous())
+        near = rank < q
+        score = torch.zeros(k, dtype=torch.float64, device=dev)
+        for j in range(k):
+            score = torch.where(near[:, j], score + D[:, j], score)
+        # selection: the m lowest scores, ties by position
+        sorder = torch.argsort(score.view(torch.int64), stable=True)
+        kept = sorted(int(i) for i in sorder[:m].tolist())
+        # the kept rows in selection order, one fp32 rounding per add
+        acc = st[kept[0]].clone()
+        for j in kept[1:]:
+            acc = acc + st[j]
+        return acc / torch.tensor(float(m), dtype=torch.float32, device=dev), kept
+
     def param_drift(self, hist, new):
         a = padded_to_canonical(hist, self.dims)
         b = padded_to_canonical(new.unsqueeze(0), self.dims)

@@ -41,7 +41,7 @@ from .models.layout import P_PAD, ModelDims
 from .models.reference import init_client_params
 from .parallel.comm import Comm, LoopbackComm
 from .parallel.sharding import ShardMap
-from .protocol.aggregation import ROBUST_TYPES, make_plan, trim_count
+from .protocol.aggregation import KRUM_TYPES, ROBUST_TYPES, krum_counts, make_plan, trim_count
 from .protocol.early_stop import GlobalEarlyStop
 from .protocol.election import OneDraw, elect_aggregator, elect_majority, select_clients
 from .protocol.verification import ThesisVerifier, Verifier, VerifierState
@@ -136,6 +136,9 @@ class RoundResult:
     epochs_run: Dict[int, int]
     stop: bool = False
     times_ms: Dict[str, float] = field(default_factory=dict)
+    # krum / multi_krum: the clients whose models the aggregate holds, in
+    # selection order (None for every other rule and when nobody was elected)
+    agg_kept: Optional[List[int]] = None
 
 
 class _TableNoise:
@@ -433,10 +436,12 @@ class Federation:
                 aggregator = el.aggregator
 
         verification_results: List[Dict] = []
+        agg_kept = None
         if aggregator is not None:
             if info:
                 log.info(f"Client {aggregator + 1} selected as aggregator")
-            robust = self.update_type in ROBUST_TYPES
+            krum = self.update_type in KRUM_TYPES
+            robust = self.update_type in ROBUST_TYPES or krum
             with self.tel.phase("aggregate"):
                 if self.update_type == "mse_avg" and cfg.compat == "reference":
                     for _ in selected:          # calculate_mse_score per client (weights unused, Q3)
@@ -448,13 +453,20 @@ class Federation:
                     else:
                         sim = self._fusion_similarity(selected)
                 ns = {c: self.clients[c].train.shape[0] for c in selected} if cfg.fedavg_sample_weighted else None
-                # (the robust rules are no (source, weight) plan: an order statistic per coordinate)
+                # (the robust rules are no (source, weight) plan: an order statistic per
+                # coordinate, or a distance-based choice of whole models)
                 plan = None if robust else make_plan(self.update_type, selected, aggregator, dev_mse, cfg.compat,
                                                      sim=sim, num_samples=ns, fusion_w=fw)
             with self.tel.phase("comm"):
                 stack = self._gather_params(list(selected) if robust else [c for c, _ in plan], selected)
             with self.tel.phase("aggregate"):
-                if robust:
+                if krum:
+                    f, _, m = krum_counts(self.update_type, len(selected), cfg.robust_trim_ratio)
+                    agg, pos = eng.krum_aggregate(stack, f, m)
+                    agg_kept = [selected[i] for i in pos]
+                    log.info(f"Aggregate keeps clients {[c + 1 for c in agg_kept]} of {[c + 1 for c in selected]} "
+                             f"({self.update_type}, f = {f})")
+                elif robust:
                     agg = eng.robust_aggregate(stack, trim_count(self.update_type, len(selected),
                                                                  cfg.robust_trim_ratio))
                 else:
@@ -515,7 +527,8 @@ class Federation:
             stop = self.early.update(metric_stats(metrics)[1])
         self.round_idx += 1
         times = self.tel.end_round(round=rnd + 1, selected=len(selected), aggregator=aggregator)
-        return RoundResult(rnd, list(selected), aggregator, metrics, verification_results, epochs_all, stop, times)
+        return RoundResult(rnd, list(selected), aggregator, metrics, verification_results, epochs_all, stop, times,
+                           agg_kept)
 
     def _verify_all(self, agg: torch.Tensor, version: int, aggregator: int, rnd: int) -> List[Dict]:
         """Every receiver verifies the broadcast aggregate (all N clients but the

@@ -111,6 +111,7 @@ class DecideArgs(ctypes.Structure):
 
 VERIFY_MAX_ROWS = 4096   # rows of one receiver's verification data the fused kernel keeps in LDS
 ROBUST_MAX_K = 1024      # models one robust_agg_kernel tile ranks (elect_wsum's row table has the same bound)
+KRUM_MAX_K = 1024        # models the krum kernels rank in LDS (fedmx_krum.hip)
 
 IPC_MAX_WORLD = 16
 IPC_MAX_CHUNKS = 64
@@ -164,6 +165,9 @@ def lib():
                 "fedmx_weighted_sum": [vp, vp, i32, i32, vp, vp],
                 "fedmx_robust_agg": [vp, vp, vp, vp, i32, i32, i32, vp],
                 "fedmx_robust_max_k": [],
+                "fedmx_krum_agg": [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+                "fedmx_krum_max_k": [],
+                "fedmx_krum_tile": [],
                 "fedmx_param_drift": [vp, i32, vp, vp, vp, vp],
                 "fedmx_standardize_lds": [vp, i32, i32, vp, vp],
                 "fedmx_cen_score": [vp, i32, vp],
@@ -210,6 +214,7 @@ def lib():
             assert L.fedmx_verify_split_args_size() == ctypes.sizeof(VerifySplitArgs)
             assert L.fedmx_ipc_max_world() == IPC_MAX_WORLD and L.fedmx_ipc_max_chunks() == IPC_MAX_CHUNKS
             assert L.fedmx_robust_max_k() == ROBUST_MAX_K
+            assert L.fedmx_krum_max_k() == KRUM_MAX_K
             _lib = L
     return _lib
 
@@ -755,6 +760,77 @@ def robust_aggregate_stack(stack: torch.Tensor, t: int, out: Optional[torch.Tens
     if out is None:
         out = torch.empty(st.shape[1], dtype=torch.float32, device=st.device)
     return robust_aggregate(st, None, int(st.shape[0]), t, out)
+
+
+def krum_workspace_size(k: int) -> int:
+    """float64 elements of the krum kernels' workspace for ``k`` models:
+    ``D[k][k]``, ``score[k]``, then the compacted kept positions (``int32[k]``
+    in the last ``k`` elements' bytes)."""
+    return k * k + 2 * k
+
+
+def krum_aggregate(base: torch.Tensor, rows_ptr: Optional[int], k: int, f: int, m: int, out: torch.Tensor,
+                   state_ptr: int = 0, workspace: Optional[torch.Tensor] = None, kept_out=None,
+                   score_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out`` = mean of the ``m`` models with the lowest Krum scores among
+    ``base[rows[j]]``, j < k (score: the sum of a model's ``max(k - f - 2, 0)``
+    smallest squared distances; ``protocol/aggregation.py``), added in
+    row-table order (fedmx_krum.hip, three launches).  ``rows_ptr``:
+    device-visible ``int64[k]``, or None for rows 0..k-1.  ``workspace``:
+    float64, at least ``krum_workspace_size(k)`` elements on ``base``'s device
+    (``[:k*k]`` the distances, then the scores unless ``score_out`` takes them,
+    then the kept positions as int32); allocated when None.  ``kept_out``: an
+    int32 ``[k]`` tensor on ``base``'s device, or a device-visible address,
+    that receives the kept mask.  With ``state_ptr`` the launches write nothing
+    when the int32 there is negative (no aggregator elected).  Raises
+    ValueError for k, f or m out of range; nothing is launched."""
+    if base.dim() != 2 or base.dtype != torch.float32 or not base.is_contiguous():
+        raise ValueError("krum_aggregate: base must be a contiguous float32 [rows, P] tensor")
+    P = int(base.shape[1])
+    if not 1 <= k <= KRUM_MAX_K:
+        raise ValueError(f"krum_aggregate: k = {k} models (1..{KRUM_MAX_K} supported)")
+    if not 1 <= m <= k:
+        raise ValueError(f"krum_aggregate: m = {m} kept models of {k}")
+    if f < 0:
+        raise ValueError(f"krum_aggregate: f = {f} poisoned models")
+    if rows_ptr is None and k > base.shape[0]:
+        raise ValueError(f"krum_aggregate: k = {k} exceeds the stack's {base.shape[0]} rows")
+    if out.dtype != torch.float32 or out.numel() != P or not out.is_contiguous() or out.device != base.device:
+        raise ValueError("krum_aggregate: out must be a contiguous float32 [P] tensor on base's device")
+    need = krum_workspace_size(k)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=base.device)
+    elif (workspace.dtype != torch.float64 or workspace.numel() < need or not workspace.is_contiguous()
+          or workspace.device != base.device):
+        raise ValueError(f"krum_aggregate: workspace must be a contiguous float64 tensor of >= {need} elements "
+                         "on base's device")
+    score_ptr = workspace.data_ptr() + 8 * k * k
+    if score_out is not None:
+        if (score_out.dtype != torch.float64 or score_out.numel() < k or not score_out.is_contiguous()
+                or score_out.device != base.device):
+            raise ValueError("krum_aggregate: score_out must be a contiguous float64 [k] tensor on base's device")
+        score_ptr = score_out.data_ptr()
+    kept_ptr = 0
+    if isinstance(kept_out, torch.Tensor):
+        if (kept_out.dtype != torch.int32 or kept_out.numel() < k or not kept_out.is_contiguous()
+                or kept_out.device != base.device):
+            raise ValueError("krum_aggregate: kept_out must be a contiguous int32 [k] tensor on base's device")
+        kept_ptr = kept_out.data_ptr()
+    elif kept_out is not None:
+        kept_ptr = int(kept_out)
+    _check(lib().fedmx_krum_agg(base.data_ptr(), rows_ptr or 0, state_ptr, out.data_ptr(), k, P, f, m,
+                                workspace.data_ptr(), score_ptr, kept_ptr,
+                                workspace.data_ptr() + 8 * (k * k + k), _stream(base.device)), "fedmx_krum_agg")
+    return out
+
+
+def krum_aggregate_stack(stack: torch.Tensor, f: int, m: int, out: Optional[torch.Tensor] = None,
+                         **kw) -> torch.Tensor:
+    """``krum_aggregate`` over a ``[k, P]`` stack in row order."""
+    st = stack.contiguous()
+    if out is None:
+        out = torch.empty(st.shape[1], dtype=torch.float32, device=st.device)
+    return krum_aggregate(st, None, int(st.shape[0]), f, m, out, **kw)
 
 
 def param_drift(hist: torch.Tensor, new: torch.Tensor, seg: torch.Tensor, to_host: bool = False):

@@ -72,7 +72,7 @@ def plan_fusion(selected: Sequence[int], sim: Dict[int, float] = None, weights: 
     return [(cid, float(x)) for cid, x in zip(selected, w)]
 
 
-UPDATE_TYPES = ("avg", "fedprox", "mse_avg", "fusion_avg", "trimmed_mean", "median")
+UPDATE_TYPES = ("avg", "fedprox", "mse_avg", "fusion_avg", "trimmed_mean", "median", "krum", "multi_krum")
 
 # Robust rules: a per-coordinate order-statistic selection over the selected
 # models, which no (source, weight) plan expresses.  For every coordinate the
@@ -100,6 +100,38 @@ def trim_count(update_type: str, k: int, ratio: float = 0.2) -> int:
             raise ValueError(f"robust_trim_ratio must be in [0, 0.5), got {ratio}")
         return min(int(ratio * k), half)
     raise ValueError(f"Not a robust update type: {update_type}")
+
+
+# Distance-based rules (Blanchard et al. 2017): whole models far from the crowd
+# are discarded, so the aggregate holds only models that clients trained.  With
+# k selected models (rows of P fp32 values, selection order) and
+# ``f, q, m = krum_counts(...)``:
+#   1. d(i, j): per coordinate e = fp32(a - b), s = (double)e * (double)e; the
+#      row zero-extended to a multiple of 256; p_l = s_l + s_{l+256} + ... in
+#      that order in f64 (l < 256); eight folds p_l += p_{l+h}, h = 128 .. 1;
+#      d = p_0, NaN -> +inf;
+#   2. score_i: model i's k - 1 distances ranked ascending (ties by the smaller
+#      j), the q lowest added in order of j in f64 (q = 0: 0.0);
+#   3. rank_i = #{l : score_l < score_i or (score_l == score_i and l < i)};
+#      model i is kept iff rank_i < m;
+#   4. per coordinate the kept values added in selection order in fp32, divided
+#      (IEEE) by (float)m  (``Engine.krum_aggregate``).
+# Like the robust rules these are no (source, weight) plan and train plainly.
+KRUM_TYPES = ("krum", "multi_krum")
+
+
+def krum_counts(update_type: str, k: int, ratio: float = 0.2):
+    """``(f, q, m)``: models assumed poisoned ``f = min(floor(ratio * k),
+    max((k - 3) // 2, 0))``, neighbours scored ``q = max(k - f - 2, 0)``, models
+    kept ``m`` (``krum``: 1, ``multi_krum``: ``k - f``)."""
+    if update_type not in KRUM_TYPES:
+        raise ValueError(f"Not a krum update type: {update_type}")
+    if k < 1:
+        raise ValueError(f"krum_counts: k = {k}")
+    if not 0.0 <= ratio < 0.5:
+        raise ValueError(f"robust_trim_ratio must be in [0, 0.5), got {ratio}")
+    f = min(int(ratio * k), max((k - 3) // 2, 0))
+    return f, max(k - f - 2, 0), 1 if update_type == "krum" else k - f
 
 
 def make_plan(update_type: str, selected: Sequence[int], aggregator: int, dev_mse: Dict[int, float] = None,

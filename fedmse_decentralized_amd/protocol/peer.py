@@ -30,7 +30,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .aggregation import ROBUST_TYPES, make_plan, trim_count
+from .aggregation import KRUM_TYPES, ROBUST_TYPES, krum_counts, make_plan, trim_count
 from .verification import VerifierState
 
 log = logging.getLogger("fedmx")
@@ -116,6 +116,9 @@ class Peer:
         stack = torch.stack([s.to(eng.store.params.device) for s in sources], 0)
         if fed.update_type in ROBUST_TYPES:   # an order statistic per coordinate, not a weighted plan
             return eng.robust_aggregate(stack, trim_count(fed.update_type, len(ids), fed.cfg.robust_trim_ratio))
+        if fed.update_type in KRUM_TYPES:     # a distance-based choice of whole models
+            f, _, m = krum_counts(fed.update_type, len(ids), fed.cfg.robust_trim_ratio)
+            return eng.krum_aggregate(stack, f, m)[0]
         dev_mse = None
         if fed.update_type == "mse_avg":
             saved = eng.store.params[self.row].clone()

@@ -123,6 +123,15 @@ def main():
         out[f"weighted_sum_k{kk}_us"] = timeit(lambda: _hip.weighted_sum(st, [1.0 / kk] * kk, out=agg_out))[0]
         out[f"robust_agg_k{kk}_us"] = timeit(lambda: _hip.robust_aggregate_stack(st, t, out=agg_out))[0]
         out[f"robust_median_k{kk}_us"] = timeit(lambda: _hip.robust_aggregate_stack(st, (kk - 1) // 2, out=agg_out))[0]
+        # krum / multi_krum (fedmx_krum.hip): the three launches a round of
+        # these rules pays behind elect_wsum, over one preallocated workspace
+        from fedmse_decentralized_amd.protocol.aggregation import krum_counts  # noqa: E402
+
+        ws = torch.empty(_hip.krum_workspace_size(kk), dtype=torch.float64, device=dev)
+        for ut in ("krum", "multi_krum"):
+            kf, _, km = krum_counts(ut, kk, 0.2)
+            out[f"{ut}_k{kk}_us"] = timeit(lambda: _hip.krum_aggregate_stack(st, kf, km, out=agg_out,
+                                                                             workspace=ws))[0]
     t0 = time.perf_counter()
     for _ in range(20):
         evaluate_clients(eng, allc, "hybrid", "AUC")
