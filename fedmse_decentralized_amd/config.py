@@ -38,7 +38,7 @@ class ExperimentConfig:
     batch_size: int = 12
     new_device: bool = True
     global_patience: int = 1
-    metric: str = "AUC"                  # "AUC" | "classification" | "time"
+    metric: str = "AUC"                  # "AUC" | "classification" | "time" | "detection" | "tpr_at_fpr"
     model_types: List[str] = field(default_factory=lambda: ["hybrid", "autoencoder"])
     update_types: List[str] = field(default_factory=lambda: ["avg", "fedprox", "mse_avg"])
     dim_features: int = 115
@@ -86,6 +86,13 @@ class ExperimentConfig:
     # "krum" / "multi_krum": the share of the selected models assumed poisoned,
     # f = floor(ratio * k), at most (k - 3) // 2 (krum_counts)
     robust_trim_ratio: float = 0.2
+    # metric "detection": the alarm threshold is the smallest validation score
+    # (the client's own held-back normal rows, under the evaluated model) with
+    # at least this share of them at or below it; in (0, 1]
+    detect_quantile: float = 0.95
+    # metric "tpr_at_fpr": the threshold is that quantile, 1 - target_fpr, of
+    # the test set's normal scores, and the metric the recall there; in [0, 1)
+    target_fpr: float = 0.01
     # --- protocol variants ---------------------------------------------------
     # "first_voter": the reference's decentralised election (first selected
     #   voter that finds an eligible candidate decides, client_trainer.py:249-285);
@@ -165,6 +172,10 @@ class ExperimentConfig:
         if self.drift_threshold_rel > 0 and self.compat != "fixed":
             raise ValueError("drift_threshold_rel > 0 replaces the reference's absolute drift rule "
                              "(src/Trainer/model_verifier.py:72-75): it needs compat='fixed'")
+        if not 0.0 < self.detect_quantile <= 1.0:
+            raise ValueError(f"detect_quantile must lie in (0, 1], got {self.detect_quantile!r}")
+        if not 0.0 <= self.target_fpr < 1.0:
+            raise ValueError(f"target_fpr must lie in [0, 1), got {self.target_fpr!r}")
 
     def resolved_init_mode(self) -> str:
         if self.init_mode == "auto":
@@ -198,6 +209,13 @@ def _str2bool(s):
 
 
 _HELP = {
+    "metric": "AUC | classification (F1 at score > 0.5) | time | detection (F1 at the threshold calibrated on "
+              "each client's validation scores, --detect-quantile) | tpr_at_fpr (recall at the threshold that "
+              "leaves --target-fpr of the normal test rows flagged)",
+    "detect_quantile": "metric detection: quantile of a client's validation scores used as its alarm "
+                       "threshold, in (0, 1] (default 0.95)",
+    "target_fpr": "metric tpr_at_fpr: false-positive rate on the normal test rows at which recall is "
+                  "reported, in [0, 1) (default 0.01)",
     "update_types": "any of: avg fedprox mse_avg fusion_avg trimmed_mean median krum multi_krum",
     "robust_trim_ratio": "share of the selected models assumed poisoned, in [0, 0.5): trimmed_mean drops that "
                          "fraction at each end of every coordinate's order, krum / multi_krum discard that "
@@ -224,7 +242,7 @@ def add_arguments(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
         elif default is None and str(f.type) in ("Optional[int]", "int"):
             p.add_argument(name, type=int, default=None)
         else:
-            p.add_argument(name, type=str, default=None)
+            p.add_argument(name, type=str, default=None, help=_HELP.get(f.name))
     # reference spelling alias
     p.add_argument("--no-Exp", dest="no_exp", type=str, default=None)
     return p

@@ -163,6 +163,10 @@ def batch_mean_scores(sse: torch.Tensor, bs: int, d_in: int) -> Tuple[float, flo
 
 class Engine:
     name = "abstract"
+    # operating point of the "detection" / "tpr_at_fpr" metrics (the
+    # federation sets them from cfg.detect_quantile / cfg.target_fpr)
+    detect_quantile = 0.95
+    target_fpr = 0.01
 
     def __init__(self, dims: ModelDims = DEFAULT_DIMS, device: Optional[torch.device] = None):
         self.dims = dims
@@ -228,6 +232,20 @@ class Engine:
         raise NotImplementedError
 
     def auc(self, scores: Sequence[torch.Tensor], labels: Sequence[torch.Tensor]) -> np.ndarray:
+        raise NotImplementedError
+
+    def detect_metrics(self, calib: Sequence[torch.Tensor], scores: Sequence[torch.Tensor],
+                       labels: Sequence[torch.Tensor], ranks: Sequence[int],
+                       calib_labels: Optional[Sequence[torch.Tensor]] = None, score_scale: float = 1.0,
+                       value: str = "f1") -> np.ndarray:
+        """float64 [8, k] (value, threshold, tp, fp, fn, tn, precision, recall)
+        per (calibration vector, test scores, labels, rank) item: the threshold
+        is the ``ranks[i]``-th smallest (0-based) cleaned calibration value
+        (of the rows whose ``calib_labels`` entry is 0, when given; NaN for a
+        rank of -1), row ``s`` is flagged iff ``s > threshold``.  float32
+        vectors are multiplied by ``score_scale`` in float32 first; NaN reads
+        as 0 and +-inf as +-DBL_MAX.  ``value``: "f1" or "recall" in row 0
+        (README "Detection thresholds", eval/metrics.py)."""
         raise NotImplementedError
 
     def standardize_ddof1(self, x: torch.Tensor) -> torch.Tensor:

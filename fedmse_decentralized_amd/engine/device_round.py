@@ -44,7 +44,10 @@ mode (tested on the GPU, and over 60 bench-shaped rounds:
 scripts/device_vs_host_long.py); the host-side RNG draws one k x (k-1) noise
 table per round in both paths (and, in the thesis variant, one fallback
 uniform).  Resume snapshots (``snapshot`` / ``restore``), latent logging,
-fault injection and the non-AUC metrics run on this path too.
+fault injection and the non-AUC metrics run on this path too
+(``classification`` and ``time`` from host copies at collect time, the
+calibrated-threshold metrics ``detection`` / ``tpr_at_fpr`` entirely on the
+side stream: ``detect_kernel`` instead of ``auc_kernel``).
 """
 from __future__ import annotations
 
@@ -57,6 +60,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from ..eval.metrics import DETECT_METRICS, detection_fields
 from ..models.layout import P_PAD
 from ..ops import _hip
 from ..protocol.aggregation import KRUM_TYPES, ROBUST_TYPES, krum_counts, trim_count
@@ -97,7 +101,8 @@ def fast_path_supported(fed) -> Optional[str]:
          "thesis variant with verification rows beyond the fused kernel's LDS buffer"),
         (fed.update_type in ("avg", "fedprox", "mse_avg", "fusion_avg", "trimmed_mean", "median", "krum",
                              "multi_krum"),
-         f"update type {fed.update_type}"),        (cfg.metric in ("AUC", "classification", "time"), f"metric {cfg.metric}"),
+         f"update type {fed.update_type}"),
+        (cfg.metric in ("AUC", "classification", "time") + DETECT_METRICS, f"metric {cfg.metric}"),
         # dropped clients leave at least one selection per round (k >= 1: the
         # election kernel needs a voter); larger drop sets take the host path
         (len({c for c in cfg.dropped_clients if 0 <= c < fed.N}) < max(1, int(cfg.num_participants * fed.N)),
@@ -131,6 +136,7 @@ class LazyRoundResult:
     epochs_run = property(lambda self: self._get("epochs_run"))
     stop = property(lambda self: self._get("stop"))
     agg_kept = property(lambda self: self._get("agg_kept"))
+    detection = property(lambda self: self._get("detection"))
 
 
 class DeviceRound:
@@ -309,6 +315,19 @@ class DeviceRound:
                 self.xsend[0, P_PAD - 1] = 0.0   # int32 0
             else:
                 self.err_n = 0   # (more than 1,150 clients on one rank: the host-side check only)
+        # calibrated-threshold metrics (eval/metrics.py DETECT_METRICS): the
+        # evaluation launches detect_kernel in auc_kernel's place; its value row
+        # takes the AUCs' way (side slot, all-reduce, report slot), all 8 rows
+        # go into a mapped ring of their own, one slot per round in flight (the
+        # plan's buffer is rewritten NSIDE rounds later, possibly before a
+        # run-ahead round is collected).  With collectives the plan writes into
+        # a zeroed [8][N] device tensor that one extra all-reduce sums.
+        self.eval_metric = cfg.metric if cfg.metric in DETECT_METRICS else "AUC"
+        self.eval_grid = (N, self.start) if (self.eval_metric != "AUC" and fed.comm.collective) else None
+        self.det_ring = None
+        if self.eval_metric != "AUC":
+            self.det_slots = self.max_pending + 2
+            self.det_ring = _hip._hiprt.MappedBuffer(self.det_slots * 8 * max(N, 1) * 8)
         self.pending: deque = deque()
         # optional: HIP-event time of every round's training launch (bench.py
         # at N > 1 measures the wait for the slowest rank's largest client)
@@ -691,15 +710,23 @@ class DeviceRound:
             if cfg.metric == "time":
                 t_ev0 = torch.cuda.Event(enable_timing=True)
                 t_ev0.record(self.side)
-            eng.evaluate_launch(fed.model_type, params=eval_params)
+            eng.evaluate_launch(fed.model_type, params=eval_params, metric=self.eval_metric, grid=self.eval_grid)
             if cfg.metric == "time":
                 t_ev1 = torch.cuda.Event(enable_timing=True)
                 t_ev1.record(self.side)
                 rec["eval_timing"] = (t_ev0, t_ev1)
             rec["eval_params"] = eval_params   # --save-latents: the plan whose latent buffers hold this round's
-            aucs_ptr = eng._plan(fed.model_type, eval_params)["aucs_buf"].dev_ptr
+            plan = eng._plan(fed.model_type, eval_params, self.eval_metric, self.eval_grid)
+            detect = self.det_ring is not None
+            aucs_ptr = plan["value_ptr"] if detect else plan["aucs_buf"].dev_ptr
+            if detect:
+                di = rnd % self.det_slots
+                det_ptr = self.det_ring.dev_ptr + di * 64 * N
+                rec["detect"] = self.det_ring.view(di * 64 * N, np.float64, 8 * N).reshape(8, N)
             if not comm.collective:
                 _hip.copy2_f64(slot_ptr, aucs_ptr, N, slot_ptr + 8 * N, side_rep.data_ptr() + 8 * N, N, dev)
+                if detect:
+                    _hip.copy_f64(det_ptr, aucs_ptr, 8 * N, dev)
             else:
                 # [AUCs | rejected counts]: one RCCL all-reduce, off the main stream.
                 # Every entry this rank does not write must be zero going in: the
@@ -711,6 +738,13 @@ class DeviceRound:
                 comm.all_reduce_inplace(side_rep)
                 _hip.copy_f64(slot_ptr, side_rep.data_ptr(), 2 * N, dev)
                 side_rep.zero_()
+                if detect:
+                    # all 8 rows: one more all-reduce on this stream (every column
+                    # has one writer, the others stay zero: cleared like side_rep)
+                    det_dev = plan["det_dev"]
+                    comm.all_reduce_inplace(det_dev)
+                    _hip.copy_f64(det_ptr, det_dev.data_ptr(), 8 * N, dev)
+                    det_dev.zero_()
             ev = torch.cuda.Event()
             ev.record(self.side)
             side["ev"] = ev
@@ -753,7 +787,11 @@ class DeviceRound:
         slot = rec["slot"]
         metrics = np.array(slot[:N], dtype=np.float64)
         rej = np.array(slot[N:2 * N], dtype=np.float64)
-        if cfg.metric != "AUC":
+        detection = None
+        if "detect" in rec:
+            # the value row came through the report slot; the rest from this round's ring slot
+            detection = detection_fields(np.array(rec["detect"], dtype=np.float64))
+        elif cfg.metric != "AUC":
             metrics = self._host_metrics(rec)
         elif bool(np.any(metrics == -1.0)):
             # a class too large for the kernel's LDS sort: exact host AUC of
@@ -809,15 +847,19 @@ class DeviceRound:
         if info:
             for i in range(N):
                 log.info(f"Client {i + 1} {cfg.metric} score: {metrics[i]}")
+        if detection is not None:
+            fed._log_detection(detection)
         if fed.write_reports:
             m_ = metrics.copy()
             fed.writer.submit(lambda m_=m_, rnd=rnd: fed._report_round(rnd, m_))
+            if detection is not None:
+                fed.writer.submit(lambda d_=detection, rnd=rnd: fed._report_detection(rnd, d_))
         fed.last_metrics = metrics
         if cfg.save_latents and fed.model_type == "hybrid" and fed.local:
             # LatentData pickles: every hosted client's test-set
             # latents of this round's evaluation.  The side slot's plan is not
             # reused before this round is collected (NSIDE > max_pending).
-            p = eng._plan(fed.model_type, rec["eval_params"])
+            p = eng._plan(fed.model_type, rec["eval_params"], self.eval_metric, self.eval_grid)
             st = eng.store
             fed.latent_log[rnd] = {fed.clients[c].name: (l.detach().cpu().numpy().astype(np.float32),
                                                          st.labels(i).astype(np.float32))
@@ -830,7 +872,7 @@ class DeviceRound:
 
             stop = fed.early.update(metric_stats(metrics)[1])
         rec.update(aggregator=aggregator, metrics=metrics, verification=verification, epochs_run=epochs_local,
-                   stop=stop, agg_kept=agg_kept, done=True)
-        for key in ("handle", "snap_slot", "slot", "report", "kept", "_keep", "event", "eval_params", "eval_timing", "train_ev"):
+                   stop=stop, agg_kept=agg_kept, detection=detection, done=True)
+        for key in ("handle", "snap_slot", "slot", "report", "kept", "detect", "_keep", "event", "eval_params", "eval_timing", "train_ev"):
             rec.pop(key, None)
         self.all_rounds.pop(rnd, None)

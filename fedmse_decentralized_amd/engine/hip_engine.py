@@ -16,6 +16,9 @@
 * ``evaluate``      -> cached plans: ``fedmx_forward_rows`` (latents / SSE of every
                        hosted client) + ``fedmx_cen_score`` + ``fedmx_auc``
                        -- src/Evaluator/evaluator.py:56-94
+                       (``detection`` / ``tpr_at_fpr``: ``fedmx_detect`` in
+                       ``fedmx_auc``'s place; not in the reference)
+* ``detect_metrics`` -> ``fedmx_detect`` (calibrated threshold + counts at it)
 * ``weighted_sum``  -> ``fedmx_weighted_sum`` -- src/Trainer/client_trainer.py:107-130
 * ``robust_aggregate`` -> ``fedmx_robust_agg`` (trimmed mean / median; not in the reference)
 * ``krum_aggregate`` -> ``fedmx_krum_agg`` (Krum / Multi-Krum; not in the reference)
@@ -32,6 +35,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from ..eval.metrics import DETECT_METRICS, detect_value_is_recall
 from ..models.layout import P_PAD, segment_ids_padded
 from ..ops import _hip, _host
 from .base import Engine, TrainHandle, TrainHParams, TrainResult
@@ -177,10 +181,14 @@ class HipEngine(Engine):
         st = self.store
         _hip.broadcast_rows(st.params, st.anchor if anchor else None, list(local_rows), agg)
 
-    def _plan(self, model_type: str, params: Optional[torch.Tensor] = None) -> dict:
+    def _plan(self, model_type: str, params: Optional[torch.Tensor] = None, metric: str = "AUC",
+              grid: Optional[tuple] = None) -> dict:
         """Cached evaluation launch plan; ``params`` (default: the live client
-        parameters) is the [C, P] buffer the forward reads."""
+        parameters) is the [C, P] buffer the forward reads.  ``metric``: "AUC",
+        or one of eval.metrics.DETECT_METRICS (``_detect_plan``)."""
         params = self.store.params if params is None else params
+        if metric in DETECT_METRICS:
+            return self._detect_plan(model_type, params, metric, grid)
         key = (model_type, params.data_ptr())
         p = self._eval_plans.get(key)
         if p is not None:
@@ -217,30 +225,119 @@ class HipEngine(Engine):
         self._eval_plans[key] = p
         return p
 
-    def evaluate_launch(self, model_type: str, params: Optional[torch.Tensor] = None) -> np.ndarray:
-        """Enqueue the full AUC evaluation of every hosted client; returns the
-        host view of the AUCs (float64 [C], valid after the next sync)."""
-        p = self._plan(model_type, params)
+    def _detect_plan(self, model_type: str, params: torch.Tensor, metric: str, grid: Optional[tuple]) -> dict:
+        """The evaluation plan of a calibrated-threshold metric: the AUC
+        plan's forward (plus every client's validation rows for ``detection``),
+        for ``hybrid`` the CEN distances of the test rows and, for
+        ``detection``, of the validation rows under the same train-latent
+        scaler (a second descriptor per client), then one ``detect_kernel``
+        descriptor per client.  The [8][C] results land in mapped host memory;
+        with ``grid = (N, first)`` in a zeroed [8][N] device tensor at columns
+        ``first ..`` instead (the device round's multi-rank all-reduce)."""
+        from ..eval.evaluator import detection_ranks
+
+        key = (model_type, params.data_ptr(), metric, float(self.detect_quantile), float(self.target_fpr), grid)
+        p = self._eval_plans.get(key)
+        if p is not None:
+            return p
+        if model_type not in ("hybrid", "autoencoder"):
+            raise ValueError(f"unknown model_type {model_type!r}")
+        st = self.store
+        C = st.num_clients
+        ids = list(range(C))
+        labels = [st.label_view(c) for c in ids]
+        with_valid = metric == "detection"
+        splits = (["train"] if model_type == "hybrid" else []) + ["test"] + (["valid"] if with_valid else [])
+        m = len(splits)
+        items = [(c, st.rows(s, c)) for c in ids for s in splits]
+        if model_type == "hybrid":
+            fwd = _hip.FwdPlan(params, items, self.dims, want_sse=False, want_latent=True)
+            lat = fwd.lat_views()
+            tr, test_lat = lat[0::m], lat[1::m]
+            n_scores = sum(int(l.shape[0]) for l in lat[1::m]) + (sum(int(l.shape[0]) for l in lat[2::m])
+                                                                  if with_valid else 0)
+            scores_all = torch.empty(n_scores, dtype=torch.float64, device=self.device)
+            # test rows first, then (detection) the validation rows: 2 C descriptors, one launch
+            cdesc, views = _hip.cen_desc(list(tr) * (2 if with_valid else 1),
+                                         list(test_lat) + (list(lat[2::m]) if with_valid else []),
+                                         scores_all, self.dims.latent)
+            scores = views[:C]
+            calib = views[C:] if with_valid else scores
+            cen, ncen, scale = torch.from_numpy(cdesc.view(np.uint8).copy()).to(self.device), len(cdesc), 1.0
+        else:
+            fwd = _hip.FwdPlan(params, items, self.dims, want_sse=True, want_latent=False)
+            sse = fwd.sse_views()
+            scores, test_lat = sse[0::m], None
+            calib = sse[1::m] if with_valid else scores
+            cen, ncen, scale = None, 0, 1.0 / self.dims.d_in
+        if grid is None:
+            det_buf = _hip._hiprt.MappedBuffer(max(8 * 8 * C, 64))   # [8][C], written straight to host memory
+            det = det_buf.view(0, np.float64, 8 * C).reshape(8, C)
+            det[:] = np.nan
+            out_ptr, stride, det_dev = det_buf.dev_ptr, C, None
+        else:
+            N, first = int(grid[0]), int(grid[1])
+            if first < 0 or first + C > N:
+                raise ValueError(f"detect plan: columns {first}..{first + C} do not fit {N} clients")
+            det_buf, det = None, None
+            det_dev = torch.zeros(8 * max(N, 1), dtype=torch.float64, device=self.device)
+            out_ptr, stride = det_dev.data_ptr() + 8 * first, N
+        ddesc = _hip.detect_desc(calib, scores, labels, detection_ranks(self, ids, metric), out_ptr, max(stride, C),
+                                 calib_labels=None if with_valid else labels, f32_scale=scale,
+                                 value_is_recall=not with_valid)
+        p = dict(fwd=fwd, cen=cen, ncen=ncen, scores=scores, calib=calib, test_lat=test_lat, labels=labels,
+                 detect=torch.from_numpy(ddesc.view(np.uint8).copy()).to(self.device), det=det, det_buf=det_buf,
+                 det_dev=det_dev, value_ptr=out_ptr, aucs=None if det is None else det[0])
+        self._eval_plans[key] = p
+        return p
+
+    def evaluate_launch(self, model_type: str, params: Optional[torch.Tensor] = None, metric: str = "AUC",
+                        grid: Optional[tuple] = None) -> np.ndarray:
+        """Enqueue the full evaluation of every hosted client; returns the
+        host view of the metric (float64 [C], valid after the next sync; None
+        for a ``grid`` plan, whose results stay on the device).  ``metric``:
+        "AUC" (forward [+ CEN] + ``auc_kernel``) or a calibrated-threshold
+        metric (``detect_kernel`` in ``auc_kernel``'s place)."""
+        p = self._plan(model_type, params, metric, grid)
         p["fwd"].run()
         if p["cen"] is not None:
             _hip.launch_cen(p["cen"], p["ncen"], self.device)
-        _hip.launch_auc(p["auc"], self.store.num_clients, self.device)
+        if metric in DETECT_METRICS:
+            _hip.launch_detect(p["detect"], self.store.num_clients, self.device)
+        else:
+            _hip.launch_auc(p["auc"], self.store.num_clients, self.device)
         return p["aucs"]
 
-    def evaluate(self, model_type: str, metric: str = "AUC", keep_latents: bool = False):
-        from ..eval.evaluator import EvalResult, evaluate_clients
+    def detect_metrics(self, calib, scores, labels, ranks, calib_labels=None, score_scale=1.0, value="f1"):
+        if not len(scores):
+            return np.zeros((8, 0), dtype=np.float64)
+        view = _hip.detect(list(calib), list(scores), list(labels), [int(j) for j in ranks],
+                           None if calib_labels is None else list(calib_labels), float(score_scale),
+                           detect_value_is_recall(value))
+        self._rt.sync()
+        return np.array(view, dtype=np.float64)
 
+    def evaluate(self, model_type: str, metric: str = "AUC", keep_latents: bool = False):
+        from ..eval.evaluator import EvalResult, detection_result, evaluate_clients
+
+        if metric in DETECT_METRICS:
+            self.evaluate_launch(model_type, metric=metric)
+            p = self._plan(model_type, metric=metric)
+            self._rt.sync()
+            return detection_result(np.array(p["det"], dtype=np.float64), self._plan_latents(p, keep_latents))
         if metric != "AUC":
             return evaluate_clients(self, list(range(self.store.num_clients)), model_type, metric, keep_latents)
         aucs = self.evaluate_launch(model_type)
         p = self._plan(model_type)
         vals = self._auc_fixup(self.fetch([aucs])[0], p["scores"], p["labels"])
-        latents = None
-        if keep_latents and p["test_lat"] is not None:
-            st = self.store
-            latents = [(l.detach().cpu().numpy().astype(np.float32), st.labels(c).astype(np.float32))
-                       for c, l in enumerate(p["test_lat"])]
-        return EvalResult(np.asarray(vals, dtype=np.float64), {}, latents)
+        return EvalResult(np.asarray(vals, dtype=np.float64), {}, self._plan_latents(p, keep_latents))
+
+    def _plan_latents(self, p: dict, keep_latents: bool):
+        if not keep_latents or p["test_lat"] is None:
+            return None
+        st = self.store
+        return [(l.detach().cpu().numpy().astype(np.float32), st.labels(c).astype(np.float32))
+                for c, l in enumerate(p["test_lat"])]
 
 
 class _VoteView:

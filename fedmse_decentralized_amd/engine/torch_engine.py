@@ -241,6 +241,45 @@ class TorchEngine(Engine):
             res.append(_host.roc_auc(sn, ln))
         return np.asarray(res, dtype=np.float64)
 
+    def detect_metrics(self, calib, scores, labels, ranks, calib_labels=None, score_scale=1.0, value="f1"):
+        from ..eval.metrics import detect_value_is_recall
+
+        want_recall = detect_value_is_recall(value)
+        scale = torch.tensor(float(score_scale), dtype=torch.float32)
+
+        def cleaned(t):
+            t = t.detach().cpu()
+            if t.dtype != torch.float64:
+                t = (t.to(torch.float32) * scale).to(torch.float64)   # one fp32 rounding, then exact
+            return torch.nan_to_num(t)   # f64: nan -> 0, +-inf -> +-DBL_MAX
+
+        nan = float("nan")
+        out = np.zeros((8, len(scores)), dtype=np.float64)
+        for i, (c, s, l, j) in enumerate(zip(calib, scores, labels, ranks)):
+            c = cleaned(c)
+            if calib_labels is not None:
+                c = c[calib_labels[i].detach().cpu() == 0]
+            j = int(j)
+            tau = nan
+            if 0 <= j < c.numel():
+                tau = float(torch.sort(c).values[j])
+                if tau == 0.0:
+                    tau = 0.0   # a selected -0.0 is reported as +0.0
+            y = l.detach().cpu() != 0
+            flag = cleaned(s) > tau
+            tp = int(torch.count_nonzero(flag & y))
+            fp = int(torch.count_nonzero(flag & ~y))
+            pos = int(torch.count_nonzero(y))
+            fn, tn = pos - tp, int(y.numel()) - pos - fp
+            if tau != tau or pos == 0 or pos == int(y.numel()):
+                precision = recall = f1 = nan
+            else:
+                precision = tp / (tp + fp) if (tp + fp) else 0.0
+                recall = tp / (tp + fn) if (tp + fn) else 0.0
+                f1 = 2 * tp / (2 * tp + fp + fn) if (2 * tp + fp + fn) else 0.0
+            out[:, i] = (recall if want_recall else f1, tau, tp, fp, fn, tn, precision, recall)
+        return out
+
     def standardize_ddof1(self, x):
         D = self.dims.d_in
         xr = x[:, :D]

@@ -8,12 +8,70 @@
 * classification metrics at a fixed score threshold (F1 / precision / recall,
   ``score > 0.5`` -> anomaly, `evaluator.py:30-48`), sklearn zero-division
   conventions (0.0 with a warning there).
+* calibrated thresholds (not in the reference; README "Detection thresholds"):
+  the rank of the calibration value used as threshold, and the per-client
+  report formed from ``Engine.detect_metrics``' rows.
 """
 from __future__ import annotations
+
+import math
+from typing import Dict
 
 import numpy as np
 
 from ..ops import _host
+
+# metrics taken at a calibrated threshold (README "Detection thresholds"):
+# "detection" calibrates on the client's own validation scores (all normal)
+# and reports F1, "tpr_at_fpr" on the test set's normal scores and reports recall
+DETECT_METRICS = ("detection", "tpr_at_fpr")
+# rows of Engine.detect_metrics' [8, k] result
+DETECT_ROWS = ("value", "threshold", "tp", "fp", "fn", "tn", "precision", "recall")
+# what a round reports per client (RoundResult.detection, EvalResult.extra)
+DETECT_FIELDS = ("threshold", "tp", "fp", "fn", "tn", "precision", "recall", "f1", "fpr")
+
+
+def calibration_rank(n_c: int, q: float) -> int:
+    """0-based rank of the calibration value used as threshold: the smallest
+    rank with at least a share ``q`` of the ``n_c`` values at or below it;
+    -1 (no threshold) without calibration values."""
+    n_c = int(n_c)
+    if n_c == 0:
+        return -1
+    return min(n_c - 1, max(0, math.ceil(q * n_c) - 1))
+
+
+def detect_value_is_recall(metric_or_value: str) -> bool:
+    if metric_or_value in ("f1", "detection"):
+        return False
+    if metric_or_value in ("recall", "tpr_at_fpr"):
+        return True
+    raise ValueError(f"detect_metrics value must be 'f1' or 'recall', got {metric_or_value!r}")
+
+
+def detection_fields(rows: np.ndarray) -> Dict[str, np.ndarray]:
+    """The per-client report of a ``[8, k]`` detect_metrics result: its rows
+    1..7 by name, plus F1 and the false-positive rate formed from the exact
+    counts (one f64 division each; NaN wherever precision is undefined)."""
+    rows = np.asarray(rows, dtype=np.float64)
+    out = {name: rows[i].copy() for i, name in enumerate(DETECT_ROWS) if i}
+    tp, fp, fn, tn = out["tp"], out["fp"], out["fn"], out["tn"]
+    undefined = np.isnan(out["precision"])
+    f1 = np.zeros(rows.shape[1], dtype=np.float64)
+    fpr = np.zeros(rows.shape[1], dtype=np.float64)
+    for i in range(rows.shape[1]):
+        den = 2 * tp[i] + fp[i] + fn[i]
+        f1[i] = np.nan if undefined[i] else (2 * tp[i] / den if den else 0.0)
+        den = fp[i] + tn[i]
+        fpr[i] = np.nan if undefined[i] else (fp[i] / den if den else 0.0)
+    out["f1"], out["fpr"] = f1, fpr
+    return out
+
+
+def detection_rows(value: np.ndarray, fields: Dict[str, np.ndarray]) -> np.ndarray:
+    """Back to ``[8, k]`` rows (the form that travels through an all-reduce)."""
+    return np.stack([np.asarray(value, dtype=np.float64)] + [np.asarray(fields[n], dtype=np.float64)
+                                                             for n in DETECT_ROWS[1:]])
 
 
 def roc_auc(labels, scores) -> float:

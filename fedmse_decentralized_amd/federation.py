@@ -34,6 +34,7 @@ from .data.prepare import ClientData, prepare_federation
 from .data.synthetic import ClientRaw, SyntheticSpec, generate_client
 from .engine import Engine, TrainHParams, make_engine
 from .eval.evaluator import evaluate_clients
+from .eval.metrics import DETECT_METRICS, detection_fields, detection_rows
 from .io import checkpoint as ckpt
 from .io import reports
 from .io.async_writer import AsyncWriter, snapshot_to_host
@@ -139,6 +140,10 @@ class RoundResult:
     # krum / multi_krum: the clients whose models the aggregate holds, in
     # selection order (None for every other rule and when nobody was elected)
     agg_kept: Optional[List[int]] = None
+    # metric "detection" / "tpr_at_fpr": per client (arrays [N], identical on
+    # every rank) threshold, tp, fp, fn, tn, precision, recall, f1, fpr at the
+    # calibrated threshold (eval/metrics.py); None for every other metric
+    detection: Optional[Dict[str, np.ndarray]] = None
 
 
 class _TableNoise:
@@ -198,6 +203,7 @@ class Federation:
             init = init[:1].expand(N, -1).clone()
         self.noise = TorchRngReplay(rng_state, self.dims) if cfg.compat == "reference" else HostNoise(self.run * 10000 + 17)
         eng = self.engine
+        eng.detect_quantile, eng.target_fpr = cfg.detect_quantile, cfg.target_fpr
         loc = [clients[c] for c in self.local]
         eng.setup([c.train for c in loc], [c.valid for c in loc], [c.test for c in loc],
                   [c.test_label for c in loc], init[self.local[0]:self.local[-1] + 1] if self.local else init[:0])
@@ -277,6 +283,19 @@ class Federation:
     def _report_round(self, rnd: int, metrics: np.ndarray) -> None:
         reports.append_round_result(self.cfg, self.run, rnd, metrics, self.model_type, self.update_type,
                                     files=self.writer.files)
+
+    def _report_detection(self, rnd: int, detection: Dict[str, np.ndarray]) -> None:
+        reports.append_detection_result(self.cfg, self.run, rnd, detection, self.model_type, self.update_type,
+                                        files=self.writer.files)
+
+    def _log_detection(self, detection: Dict[str, np.ndarray]) -> None:
+        """One INFO line per round: every client's threshold and counts at it."""
+        if log.isEnabledFor(logging.INFO):
+            d = detection
+            log.info(f"Detection at the calibrated threshold ({self.cfg.metric}): " + "; ".join(
+                f"client {i + 1} tau {d['threshold'][i]:.6g} tp {int(d['tp'][i])} fp {int(d['fp'][i])} "
+                f"fn {int(d['fn'][i])} tn {int(d['tn'][i])} f1 {d['f1'][i]:.4f} fpr {d['fpr'][i]:.4f}"
+                for i in range(self.N)))
 
     def _report_verification(self, rnd: int, vr: List[Dict]) -> None:
         if self.defer_verification:
@@ -506,9 +525,17 @@ class Federation:
             vec = np.zeros(N, dtype=np.float64)
             if self.local:   # a rank may host no client (fewer clients than ranks)
                 vec[self.local[0]:self.local[-1] + 1] = er.metrics
+            det = None
+            if cfg.metric in DETECT_METRICS:
+                det = np.zeros((8, N), dtype=np.float64)
+                if self.local:
+                    det[:, self.local[0]:self.local[-1] + 1] = detection_rows(er.metrics, er.extra)
         with self.tel.phase("comm"):
             vec = self.comm.all_reduce_sum(vec)
+            if det is not None:   # one more reduce: every column has one contributor
+                det = np.asarray(self.comm.all_reduce_sum(det), dtype=np.float64)
         metrics = np.array(vec, dtype=np.float64)
+        detection = detection_fields(det) if det is not None else None
         self.noise.iterators(N * (2 if self.model_type == "hybrid" else 1))
         if info:
             for i in range(N):
@@ -516,9 +543,13 @@ class Federation:
         if cfg.save_latents and er.latents is not None:
             names = [self.clients[c].name for c in self.local]
             self.latent_log[rnd] = {n: l for n, l in zip(names, er.latents)}
+        if detection is not None:
+            self._log_detection(detection)
         if self.write_reports:
             m_ = metrics.copy()
             self.writer.submit(lambda m_=m_, rnd=rnd: self._report_round(rnd, m_))
+            if detection is not None:
+                self.writer.submit(lambda d_=detection, rnd=rnd: self._report_detection(rnd, d_))
         self.last_metrics = metrics
         if cfg.debug_replica_check:
             self.check_replicas(rnd, selected, aggregator, metrics)
@@ -528,7 +559,7 @@ class Federation:
         self.round_idx += 1
         times = self.tel.end_round(round=rnd + 1, selected=len(selected), aggregator=aggregator)
         return RoundResult(rnd, list(selected), aggregator, metrics, verification_results, epochs_all, stop, times,
-                           agg_kept)
+                           agg_kept, detection)
 
     def _verify_all(self, agg: torch.Tensor, version: int, aggregator: int, rnd: int) -> List[Dict]:
         """Every receiver verifies the broadcast aggregate (all N clients but the

@@ -6,6 +6,9 @@
 * Verification JSONL (`src/main.py:313-326`, B.2):
   ``{round, verification_results: [{client_id, rejected_updates, is_verified}]}``.
 * Training summary JSON, indent 4 (`src/main.py:390-400`, B.3).
+* Detection JSONL (not in the reference; metrics ``detection`` / ``tpr_at_fpr``),
+  one line per round beside the results file: ``{round, metric, update_type,
+  model_type, threshold[N], tp, fp, fn, tn, precision, recall, f1, fpr}``.
 
 Written with ``json.dump`` + ``"\\n"`` exactly like the reference, so files
 are byte-identical for identical values.
@@ -46,6 +49,33 @@ def append_round_result(cfg, run: int, rnd: int, metrics: Sequence[float], model
         "update_type": update_type,
         "model_type": model_type,
         "global_loss": min(defined) if defined else (float("inf") if not len(metrics) else None),
+    }, files)
+    return path
+
+
+def detection_path(cfg, run: int, model_type: str, update_type: str) -> str:
+    """Beside the results file: ``…_detection.jsonl``."""
+    return results_path(cfg, run, model_type, update_type)[:-len("_results.json")] + "_detection.jsonl"
+
+
+def append_detection_result(cfg, run: int, rnd: int, detection: Dict[str, Sequence[float]], model_type: str,
+                            update_type: str, files=None) -> str:
+    """One line per round of a ``detection`` / ``tpr_at_fpr`` run: every
+    client's calibrated threshold, the exact counts at it and the rates formed
+    from them (an undefined figure, NaN, is written as null)."""
+    path = detection_path(cfg, run, model_type, update_type)
+
+    def vals(key, as_int=False):
+        return [None if v != v else (int(v) if as_int else float(v)) for v in detection[key]]
+
+    _append_line(path, {
+        "round": rnd + 1,
+        "metric": cfg.metric,
+        "update_type": update_type,
+        "model_type": model_type,
+        "threshold": vals("threshold"),
+        "tp": vals("tp", True), "fp": vals("fp", True), "fn": vals("fn", True), "tn": vals("tn", True),
+        "precision": vals("precision"), "recall": vals("recall"), "f1": vals("f1"), "fpr": vals("fpr"),
     }, files)
     return path
 

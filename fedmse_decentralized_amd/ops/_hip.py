@@ -64,7 +64,12 @@ AUC_DTYPE = np.dtype([
     ("n", "<i4"), ("score_is_f64", "<i4"), ("score_scale", "<f4"), ("pad", "<i4"),
 ])
 SEG_DTYPE = np.dtype([("sse", "<u8"), ("n", "<i4"), ("batch", "<i4"), ("out", "<u8")])
-
+# fedmx_detect.hip DetectDesc
+DETECT_DTYPE = np.dtype([
+    ("calib", "<u8"), ("calib_label", "<u8"), ("score", "<u8"), ("label", "<u8"), ("out", "<u8"),
+    ("n_c", "<i4"), ("n", "<i4"), ("j", "<i4"), ("calib_is_f64", "<i4"), ("score_is_f64", "<i4"),
+    ("score_scale", "<f4"), ("value_is_recall", "<i4"), ("out_stride", "<i4"),
+])
 
 
 class TrainArgs(ctypes.Structure):
@@ -172,6 +177,7 @@ def lib():
                 "fedmx_standardize_lds": [vp, i32, i32, vp, vp],
                 "fedmx_cen_score": [vp, i32, vp],
                 "fedmx_auc": [vp, i32, vp],
+                "fedmx_detect": [vp, i32, vp],
                 "fedmx_score_reduce": [vp, i32, i32, vp],
                 "fedmx_score_reduce_copy": [vp, i32, i32, vp, i32, vp],
                 "fedmx_broadcast_rows": [vp, vp, vp, i32, vp, i32, vp],
@@ -204,6 +210,7 @@ def lib():
             assert L.fedmx_fwd_desc_size() == FWD_DTYPE.itemsize
             assert L.fedmx_cen_desc_size() == CEN_DTYPE.itemsize
             assert L.fedmx_auc_desc_size() == AUC_DTYPE.itemsize
+            assert L.fedmx_detect_desc_size() == DETECT_DTYPE.itemsize
             assert L.fedmx_seg_desc_size() == SEG_DTYPE.itemsize
             assert L.fedmx_train_args_size() == ctypes.sizeof(TrainArgs)
             sz = (ctypes.c_int * 4)()
@@ -592,6 +599,68 @@ def auc(scores: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], f32_scal
     (dptr,) = rt.desc.put(desc)
     _check(lib().fedmx_auc(dptr, len(desc), rt.stream), "fedmx_auc")
     return view
+
+
+def _score_vec(t: torch.Tensor, what: str) -> int:
+    if t.dtype not in (torch.float32, torch.float64) or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"detect: {what} must be a contiguous float32 or float64 vector")
+    return 1 if t.dtype == torch.float64 else 0
+
+
+def detect_desc(calib, scores, labels, ranks, out_ptr: int, out_stride: int, calib_labels=None,
+                f32_scale: float = 1.0, value_is_recall: bool = False) -> np.ndarray:
+    """DetectDesc array (fedmx_detect.hip): item i thresholds at the
+    ``ranks[i]``-th smallest cleaned value of ``calib[i]`` (of its rows whose
+    ``calib_labels[i]`` entry is 0, when given) and writes its 8 results to
+    ``out_ptr + 8 * i``, ``out_stride`` doubles apart."""
+    n = len(scores)
+    if not (len(calib) == len(labels) == len(ranks) == n) or (calib_labels is not None and len(calib_labels) != n):
+        raise ValueError("detect: calib, scores, labels, ranks (and calib_labels) must have one entry per item")
+    if out_stride < n:
+        raise ValueError(f"detect: output stride {out_stride} is below the {n} items")
+    desc = np.zeros(n, dtype=DETECT_DTYPE)
+    for i, (c, s, l, j) in enumerate(zip(calib, scores, labels, ranks)):
+        if l.dtype != torch.int32 or l.shape[0] != s.shape[0] or not l.is_contiguous():
+            raise ValueError("detect: labels must be contiguous int32, one per score")
+        desc[i]["calib_is_f64"] = _score_vec(c, "calib")
+        desc[i]["score_is_f64"] = _score_vec(s, "scores")
+        if c.dtype != s.dtype:
+            raise ValueError("detect: calib and scores must share a dtype (one score_scale reads both)")
+        cl = None if calib_labels is None else calib_labels[i]
+        if cl is not None and (cl.dtype != torch.int32 or cl.shape[0] != c.shape[0] or not cl.is_contiguous()):
+            raise ValueError("detect: calib_labels must be contiguous int32, one per calibration value")
+        if int(j) >= int(c.shape[0]):
+            raise ValueError(f"detect: rank {int(j)} is beyond the {int(c.shape[0])} calibration values")
+        desc[i]["calib"] = c.data_ptr()
+        desc[i]["calib_label"] = 0 if cl is None else cl.data_ptr()
+        desc[i]["score"] = s.data_ptr()
+        desc[i]["label"] = l.data_ptr()
+        desc[i]["out"] = out_ptr + 8 * i
+        desc[i]["n_c"] = c.shape[0]
+        desc[i]["n"] = s.shape[0]
+        desc[i]["j"] = max(int(j), -1)
+        desc[i]["score_scale"] = f32_scale
+        desc[i]["value_is_recall"] = 1 if value_is_recall else 0
+        desc[i]["out_stride"] = out_stride
+    return desc
+
+
+def detect(calib, scores, labels, ranks, calib_labels=None, f32_scale: float = 1.0,
+           value_is_recall: bool = False) -> np.ndarray:
+    """Threshold + operating-point metrics per item.  Returns a float64 host
+    view [8, k] written by the kernel (valid after ``runtime(dev).sync()``)."""
+    dev = scores[0].device
+    rt = runtime(dev)
+    k = len(scores)
+    optr, view = rt.out.take(np.float64, 8 * k)
+    desc = detect_desc(calib, scores, labels, ranks, optr, k, calib_labels, f32_scale, value_is_recall)
+    (dptr,) = rt.desc.put(desc)
+    _check(lib().fedmx_detect(dptr, k, rt.stream), "fedmx_detect")
+    return view.reshape(8, k)
+
+
+def launch_detect(desc_dev: torch.Tensor, n: int, device):
+    _check(lib().fedmx_detect(desc_dev.data_ptr(), n, _stream(device)), "fedmx_detect")
 
 
 def launch_cen(desc_dev: torch.Tensor, n: int, device):

@@ -43,8 +43,72 @@ def timeit(fn, reps=20, warm=3):
     return float(np.median(ts)), float(np.min(ts))
 
 
+def detect_timings(eng, clients, args) -> dict:
+    """``--detect``: detect_kernel (fedmx_detect.hip) beside auc_kernel on the
+    same scores (the benchmark's 10 clients: CEN distances of each test set,
+    calibrated on the ~170 validation rows), one large client where auc_kernel
+    answers -1 (host fallback), and ms / round of the device-resident round
+    under ``--metric detection`` against ``--metric classification``."""
+    from fedmse_decentralized_amd.eval.metrics import calibration_rank
+
+    dev = eng.device
+    out = {}
+    allc = list(range(args.clients))
+    items = []
+    for c in allc:
+        items += [(c, eng.store.rows(s, c)) for s in ("train", "test", "valid")]
+    _, lat = eng.forward_rows(eng.store.params, items, False, True)
+    sc = eng.cen_scores(lat[0::3], lat[1::3])
+    vc = eng.cen_scores(lat[0::3], lat[2::3])
+    labs = [eng.store.label_view(c) for c in allc]
+    ranks = [calibration_rank(int(v.shape[0]), 0.95) for v in vc]
+    out["detect_valid_rows"] = [int(v.shape[0]) for v in vc]
+    out["detect_us"] = timeit(lambda: _hip.detect(vc, sc, labs, ranks), reps=args.reps)[0]
+    out["auc_us"] = timeit(lambda: _hip.auc(sc, labs), reps=args.reps)[0]
+    n0 = [int((lb == 0).sum()) for lb in labs]
+    out["detect_tpr_at_fpr_us"] = timeit(lambda: _hip.detect(sc, sc, labs, [calibration_rank(n, 0.99) for n in n0],
+                                                             calib_labels=labs, value_is_recall=True),
+                                         reps=args.reps)[0]
+    g = torch.Generator(device="cpu").manual_seed(5)
+    big_c = [torch.rand(10_000, dtype=torch.float64, generator=g).to(dev)]
+    big_s = [torch.rand(100_000, dtype=torch.float64, generator=g).to(dev)]
+    big_y = [(torch.rand(100_000, generator=g) < 0.5).to(torch.int32).to(dev)]
+    out["detect_large_us"] = timeit(lambda: _hip.detect(big_c, big_s, big_y, [9499]), reps=args.reps)[0]
+    view = _hip.auc(big_s, big_y)
+    out["auc_large_us"] = timeit(lambda: _hip.auc(big_s, big_y), reps=args.reps)[0]
+    _hip.runtime(dev).sync()
+    out["auc_large_result"] = float(view[0])   # -1: the class is too large for the LDS sort
+    if args.detect_rounds > 0:
+        import tempfile
+
+        from fedmse_decentralized_amd.config import ExperimentConfig
+        from fedmse_decentralized_amd.federation import Federation
+
+        for metric in ("detection", "classification", "AUC"):
+            cfg = ExperimentConfig(num_participants=0.5, epoch=args.epochs, num_rounds=10 ** 9,
+                                   network_size=args.clients, synthetic="nbaiot", compat="fixed", backend="hip",
+                                   global_early_stop=False, save_checkpoints=False, log_level="WARNING",
+                                   output_root=tempfile.mkdtemp(), metric=metric)
+            fed = Federation(cfg, "hybrid", "mse_avg", 0, write_reports=False).setup()
+            assert fed._fast is not None
+            for _ in range(20):
+                fed.run_round()
+            fed.finish()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.detect_rounds):
+                fed.run_round()
+            fed.finish()
+            torch.cuda.synchronize()
+            out[f"round_ms_{metric}"] = (time.perf_counter() - t0) / args.detect_rounds * 1e3
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--detect", action="store_true", help="only the detection-metric timings (detect_kernel beside "
+                   "auc_kernel, and ms / round under --metric detection vs classification)")
+    p.add_argument("--detect-rounds", type=int, default=200)
     p.add_argument("--epochs", type=int, default=5)
     p.add_argument("--clients", type=int, default=10)
     p.add_argument("--train-clients", type=int, default=5)
@@ -58,6 +122,10 @@ def main():
     eng = HipEngine(DEFAULT_DIMS, dev)
     eng.setup([c.train for c in clients], [c.valid for c in clients], [c.test for c in clients],
               [c.test_label for c in clients], init)
+    if args.detect:
+        out = detect_timings(eng, clients, args)
+        print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
+        return
     out = {}
     sel = list(range(args.train_clients))
     # fixed-epoch training (patience large so every epoch runs)
