@@ -1035,6 +1035,9 @@ def train(store, local_ids: Sequence[int], hp, dims, stamps: Optional[torch.Tens
     rc = lib().fedmx_train(ctypes.byref(a), k, rt.stream)
     if rc == -2:
         raise ValueError(f"fused training kernel needs batch_size >= 1, got {hp.batch_size}")
+    if rc == -3:
+        raise ValueError(f"fused training kernel takes d_in 1..127, hidden 1..31 and latent 1..15, got "
+                         f"{dims.d_in} / {dims.hidden} / {dims.latent}")
     _check(rc, "fedmx_train")
     return trk.reshape(k, hp.epochs, 2), er, be
 
