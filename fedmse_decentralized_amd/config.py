@@ -22,6 +22,10 @@ DEFAULT_EXP_TEMPLATE = (
 )
 
 
+LATENT_SCORERS = ("cen", "knn")
+KNN_MAX_K = 16   # neighbours the kNN scorer's kernel keeps in registers
+
+
 @dataclass
 class ExperimentConfig:
     # --- reference constants (src/main.py:37-71) --------------------------
@@ -93,6 +97,12 @@ class ExperimentConfig:
     # metric "tpr_at_fpr": the threshold is that quantile, 1 - target_fpr, of
     # the test set's normal scores, and the metric the recall there; in [0, 1)
     target_fpr: float = 0.01
+    # what scores a ``hybrid`` model's latents (README "Latent scorers"): "cen",
+    # the reference's distance to the train latents' centroid, or "knn", the
+    # distance to the knn_k-th nearest train latent (1 <= knn_k <= 16);
+    # ``autoencoder`` models score by reconstruction error and ignore both
+    latent_scorer: str = "cen"
+    knn_k: int = 5
     # --- protocol variants ---------------------------------------------------
     # "first_voter": the reference's decentralised election (first selected
     #   voter that finds an eligible candidate decides, client_trainer.py:249-285);
@@ -176,6 +186,10 @@ class ExperimentConfig:
             raise ValueError(f"detect_quantile must lie in (0, 1], got {self.detect_quantile!r}")
         if not 0.0 <= self.target_fpr < 1.0:
             raise ValueError(f"target_fpr must lie in [0, 1), got {self.target_fpr!r}")
+        if self.latent_scorer not in LATENT_SCORERS:
+            raise ValueError(f"latent_scorer must be one of {' | '.join(LATENT_SCORERS)}, got {self.latent_scorer!r}")
+        if isinstance(self.knn_k, bool) or not isinstance(self.knn_k, int) or not 1 <= self.knn_k <= KNN_MAX_K:
+            raise ValueError(f"knn_k must be an integer in 1..{KNN_MAX_K}, got {self.knn_k!r}")
 
     def resolved_init_mode(self) -> str:
         if self.init_mode == "auto":
@@ -216,6 +230,10 @@ _HELP = {
                        "threshold, in (0, 1] (default 0.95)",
     "target_fpr": "metric tpr_at_fpr: false-positive rate on the normal test rows at which recall is "
                   "reported, in [0, 1) (default 0.01)",
+    "latent_scorer": "what scores a hybrid model's latents: cen (distance to the train latents' centroid, the "
+                     "reference) | knn (distance to the --knn-k-th nearest train latent); autoencoder models "
+                     "ignore it (default cen)",
+    "knn_k": "latent scorer knn: which nearest train latent's distance is the score, 1..16 (default 5)",
     "update_types": "any of: avg fedprox mse_avg fusion_avg trimmed_mean median krum multi_krum",
     "robust_trim_ratio": "share of the selected models assumed poisoned, in [0, 0.5): trimmed_mean drops that "
                          "fraction at each end of every coordinate's order, krum / multi_krum discard that "
@@ -234,7 +252,7 @@ def add_arguments(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
             elem = int if f.name in ("malicious_clients", "dropped_clients") else str
             p.add_argument(name, type=elem, nargs="*", default=None, help=_HELP.get(f.name))
         elif isinstance(default, int) and not isinstance(default, bool):
-            p.add_argument(name, type=int, default=None)
+            p.add_argument(name, type=int, default=None, help=_HELP.get(f.name))
         elif isinstance(default, float):
             p.add_argument(name, type=float, default=None, help=_HELP.get(f.name))
         elif default is None and str(f.type) in ("Optional[float]", "float"):   # e.g. synthetic_alpha

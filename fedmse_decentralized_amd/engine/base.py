@@ -167,6 +167,11 @@ class Engine:
     # federation sets them from cfg.detect_quantile / cfg.target_fpr)
     detect_quantile = 0.95
     target_fpr = 0.01
+    # what scores a ``hybrid`` model's latents: "cen" (distance to the train
+    # centroid) or "knn" (distance to the knn_k-th nearest train latent); the
+    # federation sets them from cfg.latent_scorer / cfg.knn_k
+    latent_scorer = "cen"
+    knn_k = 5
 
     def __init__(self, dims: ModelDims = DEFAULT_DIMS, device: Optional[torch.device] = None):
         self.dims = dims
@@ -230,6 +235,27 @@ class Engine:
 
     def cen_scores(self, train_lat: Sequence[torch.Tensor], test_lat: Sequence[torch.Tensor]) -> List[torch.Tensor]:
         raise NotImplementedError
+
+    def knn_scores(self, train_lat: Sequence[torch.Tensor], query_lat: Sequence[torch.Tensor],
+                   k: int) -> List[torch.Tensor]:
+        """float64 [n_query] per (train latents, query latents) pair: the
+        distance of each query row to its ``min(k, n_train)``-th nearest train
+        row (README "Latent scorers").  The scaler is CEN's fit on the train
+        latents; train and query rows are both scaled as CEN scales a test row
+        (``fp32((double)v - mean)``, then ``fp32((double)t0 / scale)``); the
+        squared distance is summed in float64 over the columns in order from
+        0, a NaN sum counts as +inf, train rows equal to each other count with
+        multiplicity and a query equal to a train row is not excluded.
+        ``1 <= k <= 16``; an empty train set raises ``ValueError``."""
+        raise NotImplementedError
+
+    def latent_scores(self, train_lat: Sequence[torch.Tensor], query_lat: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+        """The scores of the configured latent scorer (``latent_scorer``, ``knn_k``)."""
+        if self.latent_scorer == "knn":
+            return self.knn_scores(train_lat, query_lat, self.knn_k)
+        if self.latent_scorer != "cen":
+            raise ValueError(f"unknown latent_scorer {self.latent_scorer!r}")
+        return self.cen_scores(train_lat, query_lat)
 
     def auc(self, scores: Sequence[torch.Tensor], labels: Sequence[torch.Tensor]) -> np.ndarray:
         raise NotImplementedError

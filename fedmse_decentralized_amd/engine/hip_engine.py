@@ -14,7 +14,8 @@
                        -- src/Trainer/model_verifier.py:79-99
 * ``adopt``         -> ``fedmx_broadcast_rows``
 * ``evaluate``      -> cached plans: ``fedmx_forward_rows`` (latents / SSE of every
-                       hosted client) + ``fedmx_cen_score`` + ``fedmx_auc``
+                       hosted client) + ``fedmx_cen_score`` (``fedmx_knn_score`` with
+                       ``latent_scorer="knn"``; not in the reference) + ``fedmx_auc``
                        -- src/Evaluator/evaluator.py:56-94
                        (``detection`` / ``tpr_at_fpr``: ``fedmx_detect`` in
                        ``fedmx_auc``'s place; not in the reference)
@@ -122,6 +123,31 @@ class HipEngine(Engine):
     def cen_scores(self, train_lat, test_lat):
         return _hip.cen_scores(train_lat, test_lat, self.dims.latent)
 
+    def knn_scores(self, train_lat, query_lat, k):
+        return _hip.knn_scores(train_lat, query_lat, self.dims.latent, int(k))
+
+    def _scorer_plan(self, train_lat, query_lat, scores_all):
+        """The configured latent scorer's part of an evaluation plan:
+        (descriptor blob on the device, its launcher, per-item score views)."""
+        if self.latent_scorer == "knn":
+            k = int(self.knn_k)
+            desc, views = _hip.knn_desc(train_lat, query_lat, scores_all, self.dims.latent, k)
+            n, y = len(desc), _hip.knn_grid_y(query_lat)
+            blob = torch.from_numpy(desc.view(np.uint8).copy()).to(self.device)
+            return blob, (lambda: _hip.launch_knn(blob, n, self.device, k=k, y=y)), views
+        if self.latent_scorer != "cen":
+            raise ValueError(f"unknown latent_scorer {self.latent_scorer!r}")
+        desc, views = _hip.cen_desc(train_lat, query_lat, scores_all, self.dims.latent)
+        n = len(desc)
+        blob = torch.from_numpy(desc.view(np.uint8).copy()).to(self.device)
+        return blob, (lambda: _hip.launch_cen(blob, n, self.device)), views
+
+    def _scorer_key(self, model_type: str) -> tuple:
+        """(latent_scorer, knn_k) as far as they change ``model_type``'s plan."""
+        if model_type != "hybrid" or self.latent_scorer == "cen":
+            return ("cen", 0)
+        return (self.latent_scorer, int(self.knn_k))
+
     def auc(self, scores, labels):
         out = self.fetch([_hip.auc(list(scores), list(labels))])[0]
         return self._auc_fixup(out, scores, labels)
@@ -189,7 +215,7 @@ class HipEngine(Engine):
         params = self.store.params if params is None else params
         if metric in DETECT_METRICS:
             return self._detect_plan(model_type, params, metric, grid)
-        key = (model_type, params.data_ptr())
+        key = (model_type, params.data_ptr(), *self._scorer_key(model_type))
         p = self._eval_plans.get(key)
         if p is not None:
             return p
@@ -206,16 +232,15 @@ class HipEngine(Engine):
             lat = fwd.lat_views()
             scores_all = torch.empty(sum(int(st.test_off[c + 1] - st.test_off[c]) for c in range(C)),
                                      dtype=torch.float64, device=self.device)
-            cdesc, scores = _hip.cen_desc(lat[0::2], lat[1::2], scores_all, self.dims.latent)
-            cdesc_dev = torch.from_numpy(cdesc.view(np.uint8).copy()).to(self.device)
+            blob, launch, scores = self._scorer_plan(lat[0::2], lat[1::2], scores_all)
             adesc = _hip.auc_desc(scores, labels, aucs_buf.dev_ptr, 1.0)
-            p = dict(fwd=fwd, cen=cdesc_dev, ncen=C, scores=scores, test_lat=lat[1::2])
+            p = dict(fwd=fwd, scorer=blob, score_launch=launch, scores=scores, test_lat=lat[1::2])
         elif model_type == "autoencoder":
             fwd = _hip.FwdPlan(params, [(c, st.rows("test", c)) for c in range(C)], self.dims,
                                want_sse=True, want_latent=False)
             scores = fwd.sse_views()
             adesc = _hip.auc_desc(scores, labels, aucs_buf.dev_ptr, 1.0 / self.dims.d_in)
-            p = dict(fwd=fwd, cen=None, ncen=0, scores=scores, test_lat=None)
+            p = dict(fwd=fwd, scorer=None, score_launch=None, scores=scores, test_lat=None)
         else:
             raise ValueError(f"unknown model_type {model_type!r}")
         p["auc"] = torch.from_numpy(adesc.view(np.uint8).copy()).to(self.device)
@@ -228,7 +253,7 @@ class HipEngine(Engine):
     def _detect_plan(self, model_type: str, params: torch.Tensor, metric: str, grid: Optional[tuple]) -> dict:
         """The evaluation plan of a calibrated-threshold metric: the AUC
         plan's forward (plus every client's validation rows for ``detection``),
-        for ``hybrid`` the CEN distances of the test rows and, for
+        for ``hybrid`` the latent scorer's distances (CEN or kNN) of the test rows and, for
         ``detection``, of the validation rows under the same train-latent
         scaler (a second descriptor per client), then one ``detect_kernel``
         descriptor per client.  The [8][C] results land in mapped host memory;
@@ -236,7 +261,8 @@ class HipEngine(Engine):
         ``first ..`` instead (the device round's multi-rank all-reduce)."""
         from ..eval.evaluator import detection_ranks
 
-        key = (model_type, params.data_ptr(), metric, float(self.detect_quantile), float(self.target_fpr), grid)
+        key = (model_type, params.data_ptr(), metric, float(self.detect_quantile), float(self.target_fpr), grid,
+               *self._scorer_key(model_type))
         p = self._eval_plans.get(key)
         if p is not None:
             return p
@@ -258,18 +284,18 @@ class HipEngine(Engine):
                                                                   if with_valid else 0)
             scores_all = torch.empty(n_scores, dtype=torch.float64, device=self.device)
             # test rows first, then (detection) the validation rows: 2 C descriptors, one launch
-            cdesc, views = _hip.cen_desc(list(tr) * (2 if with_valid else 1),
-                                         list(test_lat) + (list(lat[2::m]) if with_valid else []),
-                                         scores_all, self.dims.latent)
+            blob, launch, views = self._scorer_plan(list(tr) * (2 if with_valid else 1),
+                                                    list(test_lat) + (list(lat[2::m]) if with_valid else []),
+                                                    scores_all)
             scores = views[:C]
             calib = views[C:] if with_valid else scores
-            cen, ncen, scale = torch.from_numpy(cdesc.view(np.uint8).copy()).to(self.device), len(cdesc), 1.0
+            scale = 1.0
         else:
             fwd = _hip.FwdPlan(params, items, self.dims, want_sse=True, want_latent=False)
             sse = fwd.sse_views()
             scores, test_lat = sse[0::m], None
             calib = sse[1::m] if with_valid else scores
-            cen, ncen, scale = None, 0, 1.0 / self.dims.d_in
+            blob, launch, scale = None, None, 1.0 / self.dims.d_in
         if grid is None:
             det_buf = _hip._hiprt.MappedBuffer(max(8 * 8 * C, 64))   # [8][C], written straight to host memory
             det = det_buf.view(0, np.float64, 8 * C).reshape(8, C)
@@ -285,7 +311,7 @@ class HipEngine(Engine):
         ddesc = _hip.detect_desc(calib, scores, labels, detection_ranks(self, ids, metric), out_ptr, max(stride, C),
                                  calib_labels=None if with_valid else labels, f32_scale=scale,
                                  value_is_recall=not with_valid)
-        p = dict(fwd=fwd, cen=cen, ncen=ncen, scores=scores, calib=calib, test_lat=test_lat, labels=labels,
+        p = dict(fwd=fwd, scorer=blob, score_launch=launch, scores=scores, calib=calib, test_lat=test_lat, labels=labels,
                  detect=torch.from_numpy(ddesc.view(np.uint8).copy()).to(self.device), det=det, det_buf=det_buf,
                  det_dev=det_dev, value_ptr=out_ptr, aucs=None if det is None else det[0])
         self._eval_plans[key] = p
@@ -296,12 +322,12 @@ class HipEngine(Engine):
         """Enqueue the full evaluation of every hosted client; returns the
         host view of the metric (float64 [C], valid after the next sync; None
         for a ``grid`` plan, whose results stay on the device).  ``metric``:
-        "AUC" (forward [+ CEN] + ``auc_kernel``) or a calibrated-threshold
+        "AUC" (forward [+ latent scorer] + ``auc_kernel``) or a calibrated-threshold
         metric (``detect_kernel`` in ``auc_kernel``'s place)."""
         p = self._plan(model_type, params, metric, grid)
         p["fwd"].run()
-        if p["cen"] is not None:
-            _hip.launch_cen(p["cen"], p["ncen"], self.device)
+        if p["score_launch"] is not None:
+            p["score_launch"]()
         if metric in DETECT_METRICS:
             _hip.launch_detect(p["detect"], self.store.num_clients, self.device)
         else:

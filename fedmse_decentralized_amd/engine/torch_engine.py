@@ -233,6 +233,14 @@ class TorchEngine(Engine):
             out.append(torch.from_numpy(cen_score_numpy(trn, ten)))
         return out
 
+    def knn_scores(self, train_lat, query_lat, k):
+        out = []
+        for tr, qu in zip(train_lat, query_lat):
+            trn = tr.detach().cpu().numpy().astype(np.float32)
+            qun = qu.detach().cpu().numpy().astype(np.float32)
+            out.append(torch.from_numpy(knn_score_numpy(trn, qun, k)))
+        return out
+
     def auc(self, scores, labels):
         res = []
         for s, l in zip(scores, labels):
@@ -303,3 +311,47 @@ def cen_score_numpy(train_lat: np.ndarray, test_lat: np.ndarray) -> np.ndarray:
     t /= sc.scale_
     t64 = t.astype(np.float64)
     return np.sqrt(np.sum(t64 * t64, axis=1))
+
+
+KNN_MAX_K = 16
+
+
+def knn_score_numpy(train_lat: np.ndarray, query_lat: np.ndarray, k: int, scaler=None) -> np.ndarray:
+    """Nearest-neighbour latent score (README "Latent scorers"; the oracle of
+    ``knn_score_kernel``): the StandardScaler of ``cen_score_numpy`` fitted on
+    the train latents, the same in-place float32 transform applied to the
+    train and the query rows, squared distances summed in float64 over the
+    columns in order from 0 (NaN counts as +inf), and the square root of the
+    ``min(k, n_train)``-th smallest per query row.  ``scaler``: a fitted
+    scaler to use instead (tests nudge its mean and scale)."""
+    from ..data.scaler import StandardScaler
+
+    train_lat = np.asarray(train_lat, dtype=np.float32)
+    query_lat = np.asarray(query_lat, dtype=np.float32)
+    if not 1 <= int(k) <= KNN_MAX_K:
+        raise ValueError(f"knn: k must lie in 1..{KNN_MAX_K}, got {k!r}")
+    n, z = train_lat.shape
+    if n == 0:
+        raise ValueError("knn: a train set has no rows")
+    sc = StandardScaler().fit(train_lat) if scaler is None else scaler
+
+    def scaled(a):
+        t = a.astype(np.float32).copy()
+        t -= sc.mean_          # numpy in-place: computed in float64, stored as float32
+        t /= sc.scale_
+        return t.astype(np.float64)
+
+    x, q = scaled(train_lat), scaled(query_lat)
+    kth = min(int(k), n) - 1
+    out = np.empty(q.shape[0], dtype=np.float64)
+    chunk = max(1, (1 << 22) // n)   # <= 32 MiB of float64 distances at a time
+    with np.errstate(invalid="ignore", over="ignore"):
+        for s in range(0, q.shape[0], chunk):
+            qc = q[s:s + chunk]
+            d2 = np.zeros((qc.shape[0], n), dtype=np.float64)
+            for c in range(z):
+                df = qc[:, c:c + 1] - x[None, :, c]
+                d2 += df * df
+            d2[np.isnan(d2)] = np.inf
+            out[s:s + chunk] = np.sqrt(np.partition(d2, kth, axis=1)[:, kth])
+    return out

@@ -10,7 +10,9 @@ all hosted clients are evaluated with a handful of launches:
   .mean(1)``); AUC on the device.
 * ``hybrid`` (SAE-CEN): one ``forward_rows`` returning latents for every
   client's train and test sets; CEN scaler + distance and AUC on the device
-  (`src/Model/Centroid.py:15-35`).
+  (`src/Model/Centroid.py:15-35`).  With ``engine.latent_scorer == "knn"``
+  (not in the reference) the distance is to the ``engine.knn_k``-th nearest
+  train latent instead of the centroid (``Engine.latent_scores``).
 
 ``metric="detection"`` / ``"tpr_at_fpr"`` (not in the reference) return F1 /
 recall at a threshold calibrated per client (README "Detection thresholds");
@@ -74,9 +76,9 @@ def _evaluate_detection(engine, local_ids, model_type, metric, keep_latents) -> 
     else:
         _, lat = engine.forward_rows(st.params, items, want_sse=False, want_latent=True)
         tr, test_lat = lat[0::m], lat[1::m]
-        scores = engine.cen_scores(tr, test_lat)
+        scores = engine.latent_scores(tr, test_lat)
         # validation latents under the scaler fitted on the train latents
-        calib = engine.cen_scores(tr, lat[2::m]) if with_valid else scores
+        calib = engine.latent_scores(tr, lat[2::m]) if with_valid else scores
         scale = 1.0
     labels = [st.test_label[int(st.test_off[c]):int(st.test_off[c + 1])] for c in local_ids]
     rows = engine.detect_metrics(calib, scores, labels, detection_ranks(engine, local_ids, metric),
@@ -111,7 +113,7 @@ def evaluate_clients(engine, local_ids: Sequence[int], model_type: str, metric: 
         _, lat = engine.forward_rows(st.params, items, want_sse=False, want_latent=True)
         tr = lat[0::2]
         test_lat = lat[1::2]
-        scores = engine.cen_scores(tr, test_lat)
+        scores = engine.latent_scores(tr, test_lat)
     else:
         raise ValueError(f"unknown model_type {model_type!r}")
     labels = [st.test_label[int(st.test_off[c]):int(st.test_off[c + 1])] for c in local_ids]

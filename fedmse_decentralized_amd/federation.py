@@ -160,6 +160,8 @@ class _TableNoise:
 
 
 class Federation:
+    _scorer_ignored_logged = False
+
     def __init__(self, cfg: ExperimentConfig, model_type: str, update_type: str, run: int,
                  comm: Optional[Comm] = None, device: Optional[torch.device] = None,
                  early_stop: Optional[GlobalEarlyStop] = None, engine: Optional[Engine] = None,
@@ -204,6 +206,14 @@ class Federation:
         self.noise = TorchRngReplay(rng_state, self.dims) if cfg.compat == "reference" else HostNoise(self.run * 10000 + 17)
         eng = self.engine
         eng.detect_quantile, eng.target_fpr = cfg.detect_quantile, cfg.target_fpr
+        eng.latent_scorer, eng.knn_k = cfg.latent_scorer, cfg.knn_k
+        if self.model_type == "hybrid":
+            log.info("latent scorer: %s", "cen (distance to the train centroid)" if cfg.latent_scorer == "cen"
+                     else f"knn (distance to the {cfg.knn_k}-th nearest train latent)")
+        elif cfg.latent_scorer != "cen" and not Federation._scorer_ignored_logged:
+            Federation._scorer_ignored_logged = True   # once per process, not once per combination
+            log.info("latent scorer %s ignored: %s models score by reconstruction error", cfg.latent_scorer,
+                     self.model_type)
         loc = [clients[c] for c in self.local]
         eng.setup([c.train for c in loc], [c.valid for c in loc], [c.test for c in loc],
                   [c.test_label for c in loc], init[self.local[0]:self.local[-1] + 1] if self.local else init[:0])

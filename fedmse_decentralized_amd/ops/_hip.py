@@ -59,6 +59,14 @@ CEN_DTYPE = np.dtype([
     ("train_lat", "<u8"), ("test_lat", "<u8"), ("out", "<u8"),
     ("n_train", "<i4"), ("n_test", "<i4"), ("latent", "<i4"), ("stride", "<i4"),
 ])
+# fedmx_knn.hip KnnDesc
+KNN_DTYPE = np.dtype([
+    ("train_lat", "<u8"), ("query_lat", "<u8"), ("out", "<u8"),
+    ("n_train", "<i4"), ("n_query", "<i4"), ("latent", "<i4"), ("k", "<i4"),
+    ("train_stride", "<i4"), ("query_stride", "<i4"),
+])
+KNN_MAX_K = 16           # neighbours knn_score_kernel keeps in registers (fedmx_knn.hip)
+KNN_MAX_Y = 1024         # workgroups per descriptor a kNN launch spreads the query rows over, at most
 AUC_DTYPE = np.dtype([
     ("score", "<u8"), ("label", "<u8"), ("out", "<u8"),
     ("n", "<i4"), ("score_is_f64", "<i4"), ("score_scale", "<f4"), ("pad", "<i4"),
@@ -176,6 +184,9 @@ def lib():
                 "fedmx_param_drift": [vp, i32, vp, vp, vp, vp],
                 "fedmx_standardize_lds": [vp, i32, i32, vp, vp],
                 "fedmx_cen_score": [vp, i32, vp],
+                "fedmx_knn_score": [vp, i32, i32, i32, vp],
+                "fedmx_knn_tile_rows": [],
+                "fedmx_knn_max_k": [],
                 "fedmx_auc": [vp, i32, vp],
                 "fedmx_detect": [vp, i32, vp],
                 "fedmx_score_reduce": [vp, i32, i32, vp],
@@ -209,6 +220,7 @@ def lib():
                 f.restype = ctypes.c_int
             assert L.fedmx_fwd_desc_size() == FWD_DTYPE.itemsize
             assert L.fedmx_cen_desc_size() == CEN_DTYPE.itemsize
+            assert L.fedmx_knn_desc_size() == KNN_DTYPE.itemsize
             assert L.fedmx_auc_desc_size() == AUC_DTYPE.itemsize
             assert L.fedmx_detect_desc_size() == DETECT_DTYPE.itemsize
             assert L.fedmx_seg_desc_size() == SEG_DTYPE.itemsize
@@ -222,6 +234,7 @@ def lib():
             assert L.fedmx_ipc_max_world() == IPC_MAX_WORLD and L.fedmx_ipc_max_chunks() == IPC_MAX_CHUNKS
             assert L.fedmx_robust_max_k() == ROBUST_MAX_K
             assert L.fedmx_krum_max_k() == KRUM_MAX_K
+            assert L.fedmx_knn_max_k() == KNN_MAX_K
             _lib = L
     return _lib
 
@@ -573,6 +586,69 @@ def cen_scores(train_lat: Sequence[torch.Tensor], test_lat: Sequence[torch.Tenso
     return views
 
 
+def knn_tile_rows() -> int:
+    """Train rows one LDS tile of knn_score_kernel holds."""
+    return int(lib().fedmx_knn_tile_rows())
+
+
+def knn_grid_y(query_lat) -> int:
+    """Workgroups per descriptor of a kNN launch: one 256-row pass over the
+    largest query set, capped (more rows take more passes)."""
+    nq = max((int(q.shape[0]) for q in query_lat), default=0)
+    return max(1, min((nq + 255) // 256, KNN_MAX_Y))
+
+
+def _lat_rows(t: torch.Tensor, latent: int, what: str):
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < latent or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"knn: {what} must be float32 [n, >= {latent}] with unit column stride")
+
+
+def knn_desc(train_lat, query_lat, out: torch.Tensor, latent: int, k: int) -> Tuple[np.ndarray, List[torch.Tensor]]:
+    """KnnDesc array (fedmx_knn.hip): item i scores every row of
+    ``query_lat[i]`` against ``train_lat[i]`` into consecutive float64 slots
+    of ``out``.  Returns (descriptors, per-item views of ``out``)."""
+    if not 1 <= int(k) <= KNN_MAX_K:
+        raise ValueError(f"knn: k must lie in 1..{KNN_MAX_K}, got {k!r}")
+    if not 1 <= int(latent) <= 16:
+        raise ValueError(f"knn: latent must lie in 1..16, got {latent!r}")
+    if len(train_lat) != len(query_lat):
+        raise ValueError("knn: one query set per train set")
+    n = len(train_lat)
+    desc = np.zeros(n, dtype=KNN_DTYPE)
+    views, off = [], 0
+    for i, (tr, qu) in enumerate(zip(train_lat, query_lat)):
+        _lat_rows(tr, latent, "train latents")
+        _lat_rows(qu, latent, "query latents")
+        if tr.shape[0] == 0:
+            raise ValueError("knn: a train set has no rows")
+        desc[i]["train_lat"] = tr.data_ptr()
+        desc[i]["query_lat"] = qu.data_ptr()
+        desc[i]["out"] = out.data_ptr() + 8 * off
+        desc[i]["n_train"] = tr.shape[0]
+        desc[i]["n_query"] = qu.shape[0]
+        desc[i]["latent"] = latent
+        desc[i]["k"] = k
+        desc[i]["train_stride"] = tr.stride(0)
+        desc[i]["query_stride"] = qu.stride(0)
+        views.append(out[off:off + qu.shape[0]])
+        off += qu.shape[0]
+    if off > out.shape[0]:
+        raise ValueError(f"knn: {off} query rows do not fit the {out.shape[0]} output slots")
+    return desc, views
+
+
+def knn_scores(train_lat: Sequence[torch.Tensor], query_lat: Sequence[torch.Tensor], latent: int, k: int):
+    """float64 distance of every query row to the k-th nearest (scaled) train
+    row of its item (README "Latent scorers"); one launch for all items."""
+    dev = train_lat[0].device
+    rt = runtime(dev)
+    out_all = torch.empty(sum(int(t.shape[0]) for t in query_lat), dtype=torch.float64, device=dev)
+    desc, views = knn_desc(train_lat, query_lat, out_all, latent, k)
+    (dptr,) = rt.desc.put(desc)
+    _check(lib().fedmx_knn_score(dptr, len(desc), int(k), knn_grid_y(query_lat), rt.stream), "fedmx_knn_score")
+    return views
+
+
 def auc_desc(scores, labels, out_ptr: int, f32_scale: float = 1.0) -> np.ndarray:
     n = len(scores)
     desc = np.zeros(n, dtype=AUC_DTYPE)
@@ -665,6 +741,12 @@ def launch_detect(desc_dev: torch.Tensor, n: int, device):
 
 def launch_cen(desc_dev: torch.Tensor, n: int, device):
     _check(lib().fedmx_cen_score(desc_dev.data_ptr(), n, _stream(device)), "fedmx_cen_score")
+
+
+def launch_knn(desc_dev: torch.Tensor, n: int, device, k: int = KNN_MAX_K, y: int = 8):
+    """``k``: the launch's neighbour-list capacity, at least every
+    descriptor's k (the default holds any); ``y``: workgroups per descriptor."""
+    _check(lib().fedmx_knn_score(desc_dev.data_ptr(), n, int(k), int(y), _stream(device)), "fedmx_knn_score")
 
 
 def launch_auc(desc_dev: torch.Tensor, n: int, device):

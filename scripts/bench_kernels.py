@@ -104,8 +104,96 @@ def detect_timings(eng, clients, args) -> dict:
     return out
 
 
+def scorer_timings(eng, clients, args) -> dict:
+    """``--latent-scorer``: knn_score_kernel (fedmx_knn.hip) beside
+    cen_score_kernel in one process.  The benchmark's 10 clients (each test set
+    against its train latents, then test + validation sets as ``--metric
+    detection`` launches them) at k = 1, 5 and 16; one large client (50,000
+    train x 100,000 query rows, k = 5); the whole evaluation chain (forward +
+    scorer + AUC) of the cached plan for both scorers; and ms / round of the
+    device-resident round under either scorer."""
+    dev = eng.device
+    out = {}
+    allc = list(range(args.clients))
+    items = []
+    for c in allc:
+        items += [(c, eng.store.rows(s, c)) for s in ("train", "test", "valid")]
+    _, lat = eng.forward_rows(eng.store.params, items, False, True)
+    tr, te, va = lat[0::3], lat[1::3], lat[2::3]
+    out["train_rows"] = [int(t.shape[0]) for t in tr]
+    out["test_rows"] = [int(t.shape[0]) for t in te]
+    out["valid_rows"] = [int(t.shape[0]) for t in va]
+    Z = eng.dims.latent
+
+    def launcher(scorer, trs, qus, k=5):
+        """A cached-descriptor launch, as an evaluation plan issues it."""
+        res = torch.empty(sum(int(q.shape[0]) for q in qus), dtype=torch.float64, device=dev)
+        eng.latent_scorer, eng.knn_k = scorer, k
+        blob, launch, _ = eng._scorer_plan(list(trs), list(qus), res)
+        return lambda keep=(blob, res): launch()
+
+    reps = max(args.reps, 50)
+    out["cen_test_us"] = timeit(launcher("cen", tr, te), reps=reps)[0]
+    out["cen_test_valid_us"] = timeit(launcher("cen", list(tr) * 2, list(te) + list(va)), reps=reps)[0]
+    for k in (1, 5, 16):
+        out[f"knn_k{k}_test_us"] = timeit(launcher("knn", tr, te, k), reps=reps)[0]
+        out[f"knn_k{k}_test_valid_us"] = timeit(launcher("knn", list(tr) * 2, list(te) + list(va), k), reps=reps)[0]
+    g = torch.Generator(device="cpu").manual_seed(6)
+    big_tr = [torch.randn(50_000, Z, generator=g).to(dev)]
+    big_q = [(1.5 * torch.randn(100_000, Z, generator=g)).to(dev)]
+    out["cen_large_us"] = timeit(launcher("cen", big_tr, big_q), reps=args.reps)[0]
+    out["knn_k5_large_us"] = timeit(launcher("knn", big_tr, big_q, 5), reps=max(args.reps // 4, 5), warm=1)[0]
+    out["knn_large_grid_y"] = _hip.knn_grid_y(big_q)
+    # pairs x padded columns x (subtract + FMA): the float64 VALU work of the scan
+    cols = 4 * ((Z + 3) // 4)
+    out["knn_k5_large_f64_gops"] = 50_000 * 100_000 * cols * 2 / out["knn_k5_large_us"] / 1e3
+    # the evaluation chain of the cached plan: forward + scorer + AUC / detect
+    for metric in ("AUC", "detection"):
+        for scorer, k in (("cen", 5), ("knn", 1), ("knn", 5), ("knn", 16)):
+            eng.latent_scorer, eng.knn_k = scorer, k
+            name = f"eval_chain_{metric}_{scorer}" + (f"_k{k}" if scorer == "knn" else "") + "_us"
+            out[name] = timeit(lambda: eng.evaluate_launch("hybrid", metric=metric), reps=reps)[0]
+    eng.latent_scorer, eng.knn_k = "cen", 5
+    if args.scorer_rounds > 0:
+        import tempfile
+
+        from fedmse_decentralized_amd.config import ExperimentConfig
+        from fedmse_decentralized_amd.federation import Federation
+
+        feds = {}
+        for scorer in ("cen", "knn"):
+            cfg = ExperimentConfig(num_participants=0.5, epoch=args.epochs, num_rounds=10 ** 9,
+                                   network_size=args.clients, synthetic="nbaiot", compat="fixed", backend="hip",
+                                   global_early_stop=False, save_checkpoints=False, log_level="WARNING",
+                                   output_root=tempfile.mkdtemp(), latent_scorer=scorer, knn_k=5)
+            fed = Federation(cfg, "hybrid", "mse_avg", 0, write_reports=False).setup()
+            assert fed._fast is not None
+            for _ in range(20):
+                fed.run_round()
+            fed.finish()
+            feds[scorer] = fed
+        # alternating blocks of rounds, so both scorers see the same machine state
+        tot = {"cen": 0.0, "knn": 0.0}
+        blocks, per = 4, max(args.scorer_rounds // 4, 1)
+        for _ in range(blocks):
+            for scorer, fed in feds.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(per):
+                    fed.run_round()
+                fed.finish()
+                torch.cuda.synchronize()
+                tot[scorer] += time.perf_counter() - t0
+        for scorer in feds:
+            out[f"round_ms_{scorer}"] = tot[scorer] / (blocks * per) * 1e3
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--latent-scorer", action="store_true", help="only the latent-scorer timings (knn_score_kernel "
+                   "beside cen_score_kernel, the evaluation chain and ms / round under either scorer)")
+    p.add_argument("--scorer-rounds", type=int, default=200)
     p.add_argument("--detect", action="store_true", help="only the detection-metric timings (detect_kernel beside "
                    "auc_kernel, and ms / round under --metric detection vs classification)")
     p.add_argument("--detect-rounds", type=int, default=200)
@@ -122,8 +210,8 @@ def main():
     eng = HipEngine(DEFAULT_DIMS, dev)
     eng.setup([c.train for c in clients], [c.valid for c in clients], [c.test for c in clients],
               [c.test_label for c in clients], init)
-    if args.detect:
-        out = detect_timings(eng, clients, args)
+    if args.detect or args.latent_scorer:
+        out = (detect_timings if args.detect else scorer_timings)(eng, clients, args)
         print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
         return
     out = {}
