@@ -103,6 +103,10 @@ class ExperimentConfig:
     # ``autoencoder`` models score by reconstruction error and ignore both
     latent_scorer: str = "cen"
     knn_k: int = 5
+    # at the end of a combination, write every hosted client's deployable
+    # detector (deploy/detector.py: model, feature scaler, latent scorer state,
+    # threshold at detect_quantile) as detector.npz beside its model.cpt
+    export_detectors: bool = False
     # --- protocol variants ---------------------------------------------------
     # "first_voter": the reference's decentralised election (first selected
     #   voter that finds an eligible candidate decides, client_trainer.py:249-285);
@@ -233,6 +237,10 @@ _HELP = {
     "latent_scorer": "what scores a hybrid model's latents: cen (distance to the train latents' centroid, the "
                      "reference) | knn (distance to the --knn-k-th nearest train latent); autoencoder models "
                      "ignore it (default cen)",
+    "export_detectors": "write each hosted client's deployable detector (detector.npz: model, feature scaler, "
+                        "latent scorer state, threshold at --detect-quantile) beside its model.cpt when the "
+                        "combination ends; score traffic with python -m fedmse_decentralized_amd.detect "
+                        "(default false)",
     "knn_k": "latent scorer knn: which nearest train latent's distance is the score, 1..16 (default 5)",
     "update_types": "any of: avg fedprox mse_avg fusion_avg trimmed_mean median krum multi_krum",
     "robust_trim_ratio": "share of the selected models assumed poisoned, in [0, 0.5): trimmed_mean drops that "
@@ -247,7 +255,9 @@ def add_arguments(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
         name = "--" + f.name.replace("_", "-")
         default = getattr(d, f.name)
         if isinstance(default, bool):
-            p.add_argument(name, type=_str2bool, default=None, metavar="BOOL")
+            # (`--flag` alone reads as `--flag true`)
+            p.add_argument(name, type=_str2bool, nargs="?", const=True, default=None, metavar="BOOL",
+                           help=_HELP.get(f.name))
         elif isinstance(default, list):
             elem = int if f.name in ("malicious_clients", "dropped_clients") else str
             p.add_argument(name, type=elem, nargs="*", default=None, help=_HELP.get(f.name))

@@ -75,7 +75,16 @@ def prepare_client(raw: ClientRaw, rs: np.random.RandomState, new_device: bool =
         train=train.astype(np.float32), valid=valid.astype(np.float32),
         test=test.astype(np.float32), test_label=test_lab.astype(np.int64),
         dev_raw=dev_n, n_normal=normal.shape[0], n_abnormal=abnormal.shape[0],
+        meta={"scaler": fitted_scaler_arrays(proc, scaler)},
     )
+
+
+def fitted_scaler_arrays(proc: IoTDataProcessor, kind: str) -> dict:
+    """The float64 vectors a fitted scaler transforms with (what a deployed
+    detector needs to standardise raw rows, deploy/detector.py): ``mean_`` /
+    ``scale_`` for ``standard``, ``scale_`` / ``min_`` for ``minmax``."""
+    names = ("mean_", "scale_") if kind == "standard" else ("scale_", "min_")
+    return {"kind": kind, **{k: np.array(getattr(proc.scaler, k), dtype=np.float64) for k in names}}
 
 
 def build_dev_set(clients: Sequence[ClientData], rs: np.random.RandomState, scaler: str = "standard") -> np.ndarray:

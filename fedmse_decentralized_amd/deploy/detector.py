@@ -1,0 +1,339 @@
+"""A trained client as a deployable detector (README "Deploying a detector").
+
+A ``Detector`` bundles everything needed to turn *raw* traffic rows into
+anomaly scores and alarms: the model's dimensions, type and canonical
+parameter vector, the per-client feature scaler that ``data.prepare`` fits on
+the client's train split, for ``hybrid`` models the latent scorer with its
+state (the latent ``StandardScaler`` for ``cen``; ``knn_k`` and the train
+latents for ``knn``), and the calibrated alarm threshold.  ``save`` / ``load``
+use a plain ``.npz`` of arrays and scalars (no pickle; loads with
+``allow_pickle=False``).
+
+``score_rows_numpy`` is the scoring rule written out literally (the oracle of
+``score_rows_kernel``):
+
+1. standardise: ``IoTDataProcessor.transform(rows).astype(float32)``;
+2. forward: the engine's ``forward_rows`` on the zero-padded fp32 rows;
+3. score: ``autoencoder`` ``(double)(sse * fp32(1 / D))`` with the product in
+   fp32; ``hybrid`` + ``cen`` the CEN per-row loop under the stored latent
+   scaler; ``hybrid`` + ``knn`` ``Engine.knn_scores`` against the stored
+   train latents;
+4. clean (NaN -> 0, +-inf -> +-DBL_MAX) and flag iff ``score > threshold``
+   (a tie is normal; a NaN threshold flags nothing).
+"""
+from __future__ import annotations
+
+import json
+import zipfile
+from dataclasses import dataclass, field
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from ..data.scaler import IoTDataProcessor, StandardScaler
+from ..eval.metrics import calibration_rank
+from ..models.layout import ModelDims, canonical_to_padded
+
+FORMAT_VERSION = 1
+MODEL_TYPES = ("autoencoder", "hybrid")
+SCALER_KINDS = ("standard", "minmax")
+LATENT_SCORERS = ("cen", "knn")
+# the scaler vectors each kind stores, in the order the kernel reads them
+SCALER_FIELDS = {"standard": ("mean_", "scale_"), "minmax": ("scale_", "min_")}
+KNN_MAX_K = 16
+
+
+@dataclass
+class Detector:
+    dims: ModelDims
+    model_type: str                       # "autoencoder" | "hybrid"
+    params: np.ndarray                    # float32 [dims.num_params], canonical order
+    scaler_kind: str                      # "standard" | "minmax"
+    scaler: Dict[str, np.ndarray]         # SCALER_FIELDS[scaler_kind] -> float64 [D]
+    threshold: float = float("nan")       # alarm iff score > threshold; NaN: no alarms
+    detect_quantile: float = float("nan")  # the quantile the threshold was calibrated at
+    latent_scorer: Optional[str] = None   # hybrid: "cen" | "knn"
+    latent_mean: Optional[np.ndarray] = None    # hybrid: float64 [Z], StandardScaler of the train latents
+    latent_scale: Optional[np.ndarray] = None   # hybrid: float64 [Z]
+    knn_k: int = 0                        # knn: which nearest train latent's distance is the score
+    train_latents: Optional[np.ndarray] = None  # knn: float32 [n, Z]
+    provenance: Dict[str, str] = field(default_factory=dict)
+    version: int = FORMAT_VERSION
+
+    def __post_init__(self):
+        self.validate()
+
+    # -- consistency ---------------------------------------------------------------
+    def validate(self) -> None:
+        """ValueError unless every field has the type and shape the others imply."""
+        d = self.dims
+        if self.version != FORMAT_VERSION:
+            raise ValueError(f"detector format version {self.version!r} is not supported (this reader: "
+                             f"{FORMAT_VERSION})")
+        if self.model_type not in MODEL_TYPES:
+            raise ValueError(f"model_type must be one of {' | '.join(MODEL_TYPES)}, got {self.model_type!r}")
+        if self.scaler_kind not in SCALER_KINDS:
+            raise ValueError(f"scaler kind must be one of {' | '.join(SCALER_KINDS)}, got {self.scaler_kind!r}")
+        self.params = _arr(self.params, np.float32, (d.num_params,), "params")
+        want = SCALER_FIELDS[self.scaler_kind]
+        if set(self.scaler) != set(want):
+            raise ValueError(f"a {self.scaler_kind} scaler holds {want}, got {sorted(self.scaler)}")
+        self.scaler = {k: _arr(self.scaler[k], np.float64, (d.d_in,), f"scaler {k}") for k in want}
+        self.threshold = float(self.threshold)
+        self.detect_quantile = float(self.detect_quantile)
+        self.provenance = {str(k): str(v) for k, v in dict(self.provenance).items()}
+        if self.model_type == "autoencoder":
+            if self.latent_scorer is not None or self.latent_mean is not None or self.latent_scale is not None \
+                    or self.train_latents is not None or self.knn_k:
+                raise ValueError("an autoencoder detector scores by reconstruction error: no latent scorer state")
+            return
+        if self.latent_scorer not in LATENT_SCORERS:
+            raise ValueError(f"latent_scorer must be one of {' | '.join(LATENT_SCORERS)}, got {self.latent_scorer!r}")
+        if self.latent_mean is None or self.latent_scale is None:
+            raise ValueError("a hybrid detector holds the latent scaler's mean_ and scale_")
+        self.latent_mean = _arr(self.latent_mean, np.float64, (d.latent,), "latent mean_")
+        self.latent_scale = _arr(self.latent_scale, np.float64, (d.latent,), "latent scale_")
+        if self.latent_scorer == "knn":
+            if isinstance(self.knn_k, bool) or not 1 <= int(self.knn_k) <= KNN_MAX_K:
+                raise ValueError(f"knn_k must lie in 1..{KNN_MAX_K}, got {self.knn_k!r}")
+            self.knn_k = int(self.knn_k)
+            if self.train_latents is None:
+                raise ValueError("a knn detector holds its train latents")
+            tl = np.asarray(self.train_latents)
+            if tl.ndim != 2 or tl.shape[0] < 1:
+                raise ValueError("a knn detector needs at least one train latent row")
+            self.train_latents = _arr(tl, np.float32, (tl.shape[0], d.latent), "train latents")
+        elif self.train_latents is not None or self.knn_k:
+            raise ValueError("a cen detector holds no knn state")
+
+    # -- file ----------------------------------------------------------------------
+    def save(self, path: str) -> str:
+        """Write the bundle as ``.npz`` (numeric and string arrays only)."""
+        arrays = {
+            "version": np.array(self.version, dtype=np.int64),
+            "dims": np.array([self.dims.d_in, self.dims.hidden, self.dims.latent], dtype=np.int64),
+            "model_type": np.array(self.model_type),
+            "params": self.params,
+            "scaler_kind": np.array(self.scaler_kind),
+            "threshold": np.array(self.threshold, dtype=np.float64),
+            "detect_quantile": np.array(self.detect_quantile, dtype=np.float64),
+            "provenance": np.array(json.dumps(self.provenance, sort_keys=True)),
+        }
+        for k, v in self.scaler.items():
+            arrays["scaler_" + k] = v
+        if self.model_type == "hybrid":
+            arrays["latent_scorer"] = np.array(self.latent_scorer)
+            arrays["latent_mean_"] = self.latent_mean
+            arrays["latent_scale_"] = self.latent_scale
+            if self.latent_scorer == "knn":
+                arrays["knn_k"] = np.array(self.knn_k, dtype=np.int64)
+                arrays["train_latents"] = self.train_latents
+        with open(path, "wb") as f:   # (a file object: numpy appends no suffix)
+            np.savez(f, **arrays)
+        return path
+
+    @classmethod
+    def load(cls, path: str) -> "Detector":
+        """Read a bundle; ValueError for an unknown version, a file that needs
+        pickle, a missing array or shapes that contradict each other."""
+        try:
+            with np.load(path, allow_pickle=False) as z:
+                a = {k: z[k] for k in z.files}
+        except (zipfile.BadZipFile, OSError, EOFError) as e:
+            if isinstance(e, FileNotFoundError):
+                raise
+            raise ValueError(f"{path}: not a detector bundle ({e})") from e
+        except ValueError as e:   # numpy: "Object arrays cannot be loaded when allow_pickle=False"
+            raise ValueError(f"{path}: not a detector bundle ({e})") from e
+
+        def need(k):
+            if k not in a:
+                raise ValueError(f"{path}: detector bundle lacks {k!r}")
+            return a[k]
+
+        version = _scalar(need("version"), int, "version")
+        if version != FORMAT_VERSION:
+            raise ValueError(f"{path}: detector format version {version} is not supported (this reader: "
+                             f"{FORMAT_VERSION})")
+        dv = np.asarray(need("dims"))
+        if dv.shape != (3,) or dv.dtype.kind not in "iu":
+            raise ValueError(f"{path}: dims must be three integers")
+        dims = ModelDims(*(int(v) for v in dv))
+        model_type = _scalar(need("model_type"), str, "model_type")
+        kind = _scalar(need("scaler_kind"), str, "scaler_kind")
+        if kind not in SCALER_KINDS:
+            raise ValueError(f"{path}: unknown scaler kind {kind!r}")
+        try:
+            prov = json.loads(_scalar(need("provenance"), str, "provenance"))
+        except json.JSONDecodeError as e:
+            raise ValueError(f"{path}: provenance is not a JSON object ({e})") from e
+        if not isinstance(prov, dict):
+            raise ValueError(f"{path}: provenance is not a JSON object")
+        kw = {}
+        if model_type == "hybrid":
+            kw["latent_scorer"] = _scalar(need("latent_scorer"), str, "latent_scorer")
+            kw["latent_mean"], kw["latent_scale"] = need("latent_mean_"), need("latent_scale_")
+            if kw["latent_scorer"] == "knn":
+                kw["knn_k"] = _scalar(need("knn_k"), int, "knn_k")
+                kw["train_latents"] = need("train_latents")
+        return cls(dims=dims, model_type=model_type, params=_exact(need("params"), np.float32, "params"),
+                   scaler_kind=kind,
+                   scaler={k: _exact(need("scaler_" + k), np.float64, "scaler " + k) for k in SCALER_FIELDS[kind]},
+                   threshold=_scalar(need("threshold"), float, "threshold"),
+                   detect_quantile=_scalar(need("detect_quantile"), float, "detect_quantile"),
+                   provenance=prov, version=version, **kw)
+
+    # -- scoring pieces --------------------------------------------------------------
+    def processor(self) -> IoTDataProcessor:
+        """The fitted ``IoTDataProcessor`` this bundle's scaler came from."""
+        proc = IoTDataProcessor(self.scaler_kind)
+        for k, v in self.scaler.items():
+            setattr(proc.scaler, k, v)
+        return proc
+
+    def standardise(self, rows: np.ndarray) -> np.ndarray:
+        """Raw rows [n, D] (float64, or float32 widened exactly) -> the fp32
+        rows the model was trained on."""
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.dims.d_in:
+            raise ValueError(f"rows must be [n, {self.dims.d_in}], got {rows.shape}")
+        with np.errstate(all="ignore"):
+            return self.processor().transform(rows.astype(np.float64))[0].astype(np.float32)
+
+    def padded_params(self) -> torch.Tensor:
+        return canonical_to_padded(torch.from_numpy(self.params), self.dims)
+
+    # -- export ------------------------------------------------------------------------
+    @classmethod
+    def from_federation(cls, fed, client_id: int) -> "Detector":
+        """Client ``client_id``'s detector under its current parameters (the
+        ones the evaluation evaluates); the client must be hosted by this
+        rank.  The threshold is README "Detection thresholds"' tau: the
+        ``calibration_rank(n_valid, detect_quantile)``-th smallest cleaned
+        validation score under these parameters (NaN without validation rows)."""
+        eng, cfg = fed.engine, fed.cfg
+        st, dims = eng.store, fed.dims
+        if client_id not in fed.local:
+            raise ValueError(f"client {client_id} is not hosted by this rank")
+        loc = fed._loc(client_id)
+        client = fed.clients[client_id]
+        sc = client.meta.get("scaler")
+        if sc is None:
+            raise ValueError(f"client {client.name}: the prepared data carries no fitted scaler")
+        params = eng.canonical(st.params[loc]).detach().cpu().numpy().astype(np.float32)
+        valid = st.rows("valid", loc)
+        kw = {}
+        if fed.model_type == "hybrid":
+            _, lat = eng.forward_rows(st.params, [(loc, st.rows("train", loc)), (loc, valid)],
+                                      want_sse=False, want_latent=True)
+            train_lat = eng.fetch([lat[0]])[0].astype(np.float32)
+            zs = StandardScaler().fit(train_lat)
+            kw = dict(latent_scorer=eng.latent_scorer, latent_mean=zs.mean_, latent_scale=zs.scale_)
+            if eng.latent_scorer == "knn":
+                kw.update(knn_k=int(eng.knn_k), train_latents=train_lat)
+            calib = eng.fetch([eng.latent_scores([lat[0]], [lat[1]])[0]])[0].astype(np.float64)
+        else:
+            sse, _ = eng.forward_rows(st.params, [(loc, valid)], want_sse=True, want_latent=False)
+            calib = _ae_scores(eng.fetch([sse[0]])[0], dims.d_in)
+        calib = np.sort(np.nan_to_num(calib))
+        j = calibration_rank(calib.shape[0], cfg.detect_quantile)
+        tau = float(calib[j]) if j >= 0 else float("nan")
+        if tau == 0.0:
+            tau = 0.0   # a selected -0.0 is reported as +0.0
+        prov = {"client": client.name, "client_id": str(client_id), "model_type": fed.model_type,
+                "update_type": fed.update_type, "rounds": str(fed.round_idx), "run": str(fed.run),
+                "experiment": cfg.experiment_name}
+        return cls(dims=dims, model_type=fed.model_type, params=params, scaler_kind=sc["kind"],
+                   scaler={k: np.asarray(sc[k], dtype=np.float64) for k in SCALER_FIELDS[sc["kind"]]},
+                   threshold=tau, detect_quantile=float(cfg.detect_quantile), provenance=prov, **kw)
+
+
+def _arr(a, dtype, shape: Tuple[int, ...], what: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype.kind not in "fiu" or a.shape != shape:
+        raise ValueError(f"{what} must be a numeric array of shape {shape}, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _exact(a, dtype, what: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype != np.dtype(dtype):
+        raise ValueError(f"{what} must be stored as {np.dtype(dtype).name}, got {a.dtype}")
+    return a
+
+
+def _scalar(a, typ, what: str):
+    a = np.asarray(a)
+    kinds = {int: "iu", float: "f", str: "U"}[typ]
+    if a.shape != () or a.dtype.kind not in kinds:
+        raise ValueError(f"{what} must be one {typ.__name__}, got {a.dtype} {a.shape}")
+    return typ(a[()])
+
+
+def _ae_scores(sse: np.ndarray, d_in: int) -> np.ndarray:
+    """(double)(sse * fp32(1 / D)), the product in fp32: how auc_kernel and
+    detect_kernel read an autoencoder score."""
+    with np.errstate(all="ignore"):
+        return (np.asarray(sse, dtype=np.float32) * np.float32(1.0 / d_in)).astype(np.float64)
+
+
+def cen_scores_stored(lat: np.ndarray, mean: np.ndarray, scale: np.ndarray) -> np.ndarray:
+    """cen_score_kernel's per-row loop under a stored scaler: per column
+    ``t0 = fp32((double)z - mean)``, ``t1 = fp32((double)t0 / scale)``, the
+    squares accumulated in float64 in column order from 0, then the root."""
+    with np.errstate(all="ignore"):
+        t = np.asarray(lat, dtype=np.float32).copy()
+        t -= mean          # numpy in-place: computed in float64, stored as float32
+        t /= scale
+        t64 = t.astype(np.float64)
+        acc = np.zeros(t64.shape[0], dtype=np.float64)
+        for j in range(t64.shape[1]):
+            acc += t64[:, j] * t64[:, j]
+        return np.sqrt(acc)
+
+
+def clean_and_flag(scores: np.ndarray, threshold: float):
+    """(cleaned float64 scores, uint8 flags, alarm count)."""
+    s = np.nan_to_num(np.asarray(scores, dtype=np.float64))
+    with np.errstate(invalid="ignore"):
+        flags = (s > threshold).astype(np.uint8)
+    return s, flags, int(flags.sum())
+
+
+def score_rows_numpy(detector: Detector, rows: np.ndarray, engine=None, want_latents: bool = False):
+    """The scoring rule, step by step, on the host: ``(scores float64 [n],
+    flags uint8 [n], alarms)`` (plus the fp32 latents with ``want_latents``;
+    None for an autoencoder).  ``engine``: whose ``forward_rows`` (and, for
+    knn, ``knn_scores``) run steps 2 and 3; default a ``TorchEngine`` on the CPU."""
+    from ..engine.base import pad_features
+
+    det = detector
+    if engine is None:
+        from ..engine.torch_engine import TorchEngine
+
+        engine = TorchEngine(det.dims, torch.device("cpu"))
+    if engine.dims != det.dims:
+        raise ValueError(f"the engine's dimensions {engine.dims} are not the detector's {det.dims}")
+    x = det.standardise(rows)
+    n = x.shape[0]
+    hybrid = det.model_type == "hybrid"
+    if n == 0:
+        lat0 = np.zeros((0, det.dims.latent), np.float32) if hybrid else None
+        out = (np.zeros(0, np.float64), np.zeros(0, np.uint8), 0)
+        return out + (lat0,) if want_latents else out
+    params = det.padded_params().unsqueeze(0).to(engine.device)
+    xt = torch.from_numpy(pad_features(x)).to(engine.device)
+    sse, lat = engine.forward_rows(params, [(0, xt)], want_sse=not hybrid, want_latent=hybrid)
+    lat_np = None
+    if not hybrid:
+        scores = _ae_scores(engine.fetch([sse[0]])[0], det.dims.d_in)
+    else:
+        lat_np = engine.fetch([lat[0]])[0].astype(np.float32)
+        if det.latent_scorer == "cen":
+            scores = cen_scores_stored(lat_np, det.latent_mean, det.latent_scale)
+        else:
+            tr = torch.from_numpy(det.train_latents).to(engine.device)
+            scores = engine.fetch([engine.knn_scores([tr], [lat[0]], det.knn_k)[0]])[0].astype(np.float64)
+    out = clean_and_flag(scores, det.threshold)
+    return out + (lat_np,) if want_latents else out

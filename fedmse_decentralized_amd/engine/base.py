@@ -274,6 +274,17 @@ class Engine:
         (README "Detection thresholds", eval/metrics.py)."""
         raise NotImplementedError
 
+    def score_rows(self, detectors: Sequence, rows: Sequence, want_latents: bool = False) -> List[tuple]:
+        """Score raw traffic with deployed detectors (``deploy.Detector``;
+        README "Deploying a detector").  ``rows[i]``: the raw feature rows
+        ``[n_i, D]`` for ``detectors[i]``, float64 or float32 (numpy, or a
+        tensor).  Returns per detector ``(scores float64 [n], flags uint8 [n],
+        alarms int)`` as numpy arrays: the cleaned score of every row, 1 where
+        ``score > threshold``, and the number of flagged rows; with
+        ``want_latents`` a fourth entry, the fp32 latents ``[n, Z]`` (None for
+        an autoencoder).  The detectors' dimensions need not be the engine's."""
+        raise NotImplementedError
+
     def standardize_ddof1(self, x: torch.Tensor) -> torch.Tensor:
         """(x - mean) / (std_ddof1 + 1e-8) over the real D columns
         (`src/Trainer/client_trainer.py:220-223`)."""

@@ -20,6 +20,9 @@
                        (``detection`` / ``tpr_at_fpr``: ``fedmx_detect`` in
                        ``fedmx_auc``'s place; not in the reference)
 * ``detect_metrics`` -> ``fedmx_detect`` (calibrated threshold + counts at it)
+* ``score_rows``    -> ``fedmx_score_rows`` (deployed detectors: raw rows -> scores, alarm
+                       flags and counts in one launch; ``fedmx_knn_score`` after it for
+                       kNN detectors; not in the reference)
 * ``weighted_sum``  -> ``fedmx_weighted_sum`` -- src/Trainer/client_trainer.py:107-130
 * ``robust_aggregate`` -> ``fedmx_robust_agg`` (trimmed mean / median; not in the reference)
 * ``krum_aggregate`` -> ``fedmx_krum_agg`` (Krum / Multi-Krum; not in the reference)
@@ -156,6 +159,78 @@ class HipEngine(Engine):
         for i in np.flatnonzero(out == -1.0):   # class too large for the LDS sort: exact host path
             s = scores[i].detach().double().cpu().numpy()
             out[i] = _host.roc_auc(np.nan_to_num(s), labels[i].cpu().numpy())
+        return out
+
+    def store_device(self) -> torch.device:
+        """The device with its index, as tensors moved to ``self.device`` report it."""
+        return self._seg.device
+
+    def _score_state(self, det):
+        """The detector's constants on the device (uploaded once per detector
+        object): score_rows_kernel's state and, for knn, the train latents."""
+        hit = getattr(det, "_hip_state", None)
+        if hit is not None and hit[0].device == self.store_device():
+            hit[0].threshold = float(det.threshold)   # (the one field a user re-tunes in place)
+            return hit
+        sc = det.scaler
+        a, b = (sc["mean_"], sc["scale_"]) if det.scaler_kind == "standard" else (sc["scale_"], sc["min_"])
+        cen = det.model_type == "hybrid" and det.latent_scorer == "cen"
+        kind = _hip.SCORE_KIND_AE if det.model_type == "autoencoder" else (_hip.SCORE_KIND_CEN if cen else 0)
+        state = _hip.ScoreState(det.padded_params().to(self.device).contiguous(), det.dims, a, b,
+                                det.scaler_kind == "minmax", kind, det.threshold,
+                                det.latent_mean if cen else None, det.latent_scale if cen else None)
+        train = torch.from_numpy(det.train_latents).to(self.device) if kind == 0 else None
+        det._hip_state = (state, train)
+        return det._hip_state
+
+    def score_rows(self, detectors, rows, want_latents=False):
+        """One ``score_rows_kernel`` launch over every detector's rows; a knn
+        detector's rows leave it as latents and take ``knn_score_kernel`` after
+        it (one launch per k), the clean-and-compare of those on the host."""
+        from ..deploy.detector import clean_and_flag
+
+        if len(detectors) != len(rows):
+            raise ValueError("score_rows: one block of rows per detector")
+        xs = []
+        for x in rows:
+            if not torch.is_tensor(x):
+                x = np.ascontiguousarray(x)
+                if x.dtype not in (np.float32, np.float64):
+                    x = x.astype(np.float64)
+                x = torch.from_numpy(x)
+            xs.append(x.to(self.device).contiguous())
+        out: List[Optional[tuple]] = [None] * len(detectors)
+        live = [i for i, x in enumerate(xs) if x.shape[0] > 0]
+        for i in set(range(len(xs))) - set(live):   # no rows: nothing to launch
+            hyb = detectors[i].model_type == "hybrid"
+            lat0 = (np.zeros((0, detectors[i].dims.latent), np.float32) if hyb else None,) if want_latents else ()
+            if xs[i].dim() != 2 or xs[i].shape[1] != detectors[i].dims.d_in:
+                raise ValueError(f"rows must be [n, {detectors[i].dims.d_in}], got {tuple(xs[i].shape)}")
+            out[i] = (np.zeros(0, np.float64), np.zeros(0, np.uint8), 0) + lat0
+        if not live:
+            return out
+        states = [self._score_state(detectors[i]) for i in live]
+        res, alarms = _hip.score_rows([s for s, _ in states], [xs[i] for i in live],
+                                      want_latents=want_latents)
+        knn = [j for j, (s, _) in enumerate(states) if s.kind == 0]
+        knn_scores = {}
+        for k in sorted({detectors[live[j]].knn_k for j in knn}):
+            for z in sorted({detectors[live[j]].dims.latent for j in knn if detectors[live[j]].knn_k == k}):
+                js = [j for j in knn if detectors[live[j]].knn_k == k and detectors[live[j]].dims.latent == z]
+                views = _hip.knn_scores([states[j][1] for j in js], [res[j][2] for j in js], z, k)
+                knn_scores.update(zip(js, views))
+        self._rt.sync()
+        counts = alarms.cpu().numpy()
+        for j, i in enumerate(live):
+            sc, fl, la = res[j]
+            la = la.cpu().numpy() if (la is not None and want_latents) else None
+            if j in knn_scores:
+                s, f, a = clean_and_flag(knn_scores[j].cpu().numpy(), detectors[i].threshold)
+            else:
+                s, f, a = sc.cpu().numpy(), fl.cpu().numpy(), int(counts[j])
+            if want_latents and detectors[i].model_type != "hybrid":
+                la = None
+            out[i] = (s, f, a) + ((la,) if want_latents else ())
         return out
 
     def standardize_ddof1(self, x):

@@ -288,6 +288,18 @@ class TorchEngine(Engine):
             out[:, i] = (recall if want_recall else f1, tau, tp, fp, fn, tn, precision, recall)
         return out
 
+    def score_rows(self, detectors, rows, want_latents=False):
+        from ..deploy.detector import score_rows_numpy
+
+        if len(detectors) != len(rows):
+            raise ValueError("score_rows: one block of rows per detector")
+        out = []
+        for det, x in zip(detectors, rows):
+            x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+            eng = self if det.dims == self.dims else TorchEngine(det.dims, self.device)
+            out.append(score_rows_numpy(det, x, engine=eng, want_latents=want_latents))
+        return out
+
     def standardize_ddof1(self, x):
         D = self.dims.d_in
         xr = x[:, :D]

@@ -754,6 +754,8 @@ class Federation:
             for i, c in enumerate(self.local):
                 vec[c] = float(er.metrics[i])
             self.last_metrics = self.comm.all_reduce_sum(vec).numpy()
+        if cfg.export_detectors:
+            self.export_detectors()
         self.writer.flush()
         if cfg.save_latents and self.latent_log:
             parts = self.comm.all_gather_object(self.latent_log)
@@ -766,6 +768,20 @@ class Federation:
                                     f"Run_{self.run}/latent_{self.model_type}_{self.update_type}.pkl")
                 ckpt.save_latents(path, merged)
         return metric_stats(self.last_metrics)[2]
+
+    def export_detectors(self) -> List[str]:
+        """Write ``detector.npz`` (deploy/detector.py) beside the ``model.cpt``
+        of every client this rank hosts, from the clients' current parameters;
+        returns the paths.  Collects the rounds still in flight first."""
+        from .deploy.detector import Detector
+
+        self.finish()
+        paths = []
+        for c in self.local:
+            os.makedirs(self.save_dirs[c], exist_ok=True)
+            paths.append(Detector.from_federation(self, c).save(os.path.join(self.save_dirs[c], "detector.npz")))
+        log.info(f"Exported {len(paths)} detectors ({self.model_type}, {self.update_type})")
+        return paths
 
     # -- resume ---------------------------------------------------------------------
     def snapshot(self) -> Dict:

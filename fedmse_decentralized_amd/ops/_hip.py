@@ -78,6 +78,14 @@ DETECT_DTYPE = np.dtype([
     ("n_c", "<i4"), ("n", "<i4"), ("j", "<i4"), ("calib_is_f64", "<i4"), ("score_is_f64", "<i4"),
     ("score_scale", "<f4"), ("value_is_recall", "<i4"), ("out_stride", "<i4"),
 ])
+# fedmx_score.hip ScoreDesc
+SCORE_DTYPE = np.dtype([
+    ("params", "<u8"), ("raw", "<u8"), ("sc_a", "<u8"), ("sc_b", "<u8"), ("z_mean", "<u8"), ("z_scale", "<u8"),
+    ("score", "<u8"), ("flag", "<u8"), ("lat", "<u8"), ("alarms", "<u8"), ("threshold", "<f8"),
+    ("nrows", "<i4"), ("d_in", "<i4"), ("hidden", "<i4"), ("latent", "<i4"), ("flags", "<i4"), ("score_scale", "<f4"),
+])
+SCORE_RAW_F64, SCORE_MINMAX, SCORE_KIND_AE, SCORE_KIND_CEN = 1, 2, 4, 8
+SCORE_CHUNK_ROWS = 64    # rows a score_rows workgroup takes per pass: four waves, one 16-row tile each
 
 
 class TrainArgs(ctypes.Structure):
@@ -189,6 +197,8 @@ def lib():
                 "fedmx_knn_max_k": [],
                 "fedmx_auc": [vp, i32, vp],
                 "fedmx_detect": [vp, i32, vp],
+                "fedmx_score_rows": [vp, i32, vp],
+                "fedmx_score_chunk_rows": [],
                 "fedmx_score_reduce": [vp, i32, i32, vp],
                 "fedmx_score_reduce_copy": [vp, i32, i32, vp, i32, vp],
                 "fedmx_broadcast_rows": [vp, vp, vp, i32, vp, i32, vp],
@@ -223,6 +233,8 @@ def lib():
             assert L.fedmx_knn_desc_size() == KNN_DTYPE.itemsize
             assert L.fedmx_auc_desc_size() == AUC_DTYPE.itemsize
             assert L.fedmx_detect_desc_size() == DETECT_DTYPE.itemsize
+            assert L.fedmx_score_desc_size() == SCORE_DTYPE.itemsize
+            assert L.fedmx_score_chunk_rows() == SCORE_CHUNK_ROWS
             assert L.fedmx_seg_desc_size() == SEG_DTYPE.itemsize
             assert L.fedmx_train_args_size() == ctypes.sizeof(TrainArgs)
             sz = (ctypes.c_int * 4)()
@@ -737,6 +749,139 @@ def detect(calib, scores, labels, ranks, calib_labels=None, f32_scale: float = 1
 
 def launch_detect(desc_dev: torch.Tensor, n: int, device):
     _check(lib().fedmx_detect(desc_dev.data_ptr(), n, _stream(device)), "fedmx_detect")
+
+
+# ---------------------------------------------------------------------------
+# deployed detectors (fedmx_score.hip)
+SCORE_RESIDENT = 2 * 256   # score_rows workgroups resident at once (77 KB of LDS each: 2 per CU, 256 CUs)
+
+
+def score_rows_per_block(total_rows: int) -> int:
+    """Rows per score_rows workgroup (a multiple of the 64-row pass): about
+    two rounds of residency over the chip, so the grid fills it and the 37 KB
+    weight staging of a workgroup is spread over many passes on big inputs."""
+    fixed = int(os.environ.get("FEDMX_SCORE_ROWS_PER_BLOCK", "0"))   # A/B override
+    if fixed > 0:
+        return -(-fixed // SCORE_CHUNK_ROWS) * SCORE_CHUNK_ROWS
+    per = -(-int(total_rows) // (2 * SCORE_RESIDENT))
+    return max(SCORE_CHUNK_ROWS, -(-per // SCORE_CHUNK_ROWS) * SCORE_CHUNK_ROWS)
+
+
+class ScoreState:
+    """One detector's constants in device memory: the padded parameter
+    vector, the feature scaler's two float64 vectors and, for CEN, the latent
+    scaler's.  ``kind``: SCORE_KIND_AE, SCORE_KIND_CEN or 0 (latents only)."""
+
+    def __init__(self, params_padded: torch.Tensor, dims, sc_a: np.ndarray, sc_b: np.ndarray, minmax: bool,
+                 kind: int, threshold: float, z_mean: Optional[np.ndarray] = None,
+                 z_scale: Optional[np.ndarray] = None):
+        dev = params_padded.device
+        if params_padded.dtype != torch.float32 or params_padded.numel() != 9216 or not params_padded.is_contiguous():
+            raise ValueError("score_rows: params must be one contiguous padded float32 vector")
+        sc_a = np.ascontiguousarray(sc_a, dtype=np.float64)
+        sc_b = np.ascontiguousarray(sc_b, dtype=np.float64)
+        if sc_a.shape != (dims.d_in,) or sc_b.shape != (dims.d_in,):
+            raise ValueError(f"score_rows: the feature scaler must hold {dims.d_in} values per vector")
+        if kind not in (0, SCORE_KIND_AE, SCORE_KIND_CEN):
+            raise ValueError(f"score_rows: unknown score kind {kind!r}")
+        self.params, self.dims, self.device = params_padded, dims, dev
+        self.minmax, self.kind, self.threshold = bool(minmax), int(kind), float(threshold)
+        self.scaler = torch.from_numpy(np.stack([sc_a, sc_b])).to(dev)
+        self.zscaler = None
+        if kind == SCORE_KIND_CEN:
+            z_mean = np.ascontiguousarray(z_mean, dtype=np.float64)
+            z_scale = np.ascontiguousarray(z_scale, dtype=np.float64)
+            if z_mean.shape != (dims.latent,) or z_scale.shape != (dims.latent,):
+                raise ValueError(f"score_rows: the latent scaler must hold {dims.latent} values per vector")
+            self.zscaler = torch.from_numpy(np.stack([z_mean, z_scale])).to(dev)
+
+
+def score_desc(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], scores, flags, lats, alarms: torch.Tensor,
+               rows_per_block: Optional[int] = None) -> np.ndarray:
+    """ScoreDesc array (fedmx_score.hip): item i scores the raw rows
+    ``rows[i]`` ([n, d_in], float64 or float32, contiguous) with detector
+    ``states[i]`` into ``scores[i]`` (float64 [n]) and ``flags[i]`` (uint8 [n];
+    both None for a latents-only item), its latents into ``lats[i]`` (float32
+    [n, latent] or None), and adds its alarm count to ``alarms[i]`` (int32).
+    Every item is cut into blocks of ``rows_per_block`` rows, one workgroup each."""
+    n_items = len(states)
+    if not (len(rows) == len(scores) == len(flags) == len(lats) == n_items) or alarms.numel() < n_items:
+        raise ValueError("score_rows: one rows / scores / flags / latents / alarm slot per detector")
+    if alarms.dtype != torch.int32 or not alarms.is_contiguous():
+        raise ValueError("score_rows: the alarm counters must be contiguous int32")
+    sizes = np.array([int(x.shape[0]) for x in rows], dtype=np.int64)
+    rpb = rows_per_block or score_rows_per_block(int(sizes.sum()))
+    if rpb % SCORE_CHUNK_ROWS:
+        raise ValueError(f"score_rows: rows per block must be a multiple of {SCORE_CHUNK_ROWS}")
+    parts = []
+    for i, (st, x, sc, fl, la) in enumerate(zip(states, rows, scores, flags, lats)):
+        n, dims = int(sizes[i]), st.dims
+        if x.dim() != 2 or x.shape[1] != dims.d_in or x.dtype not in (torch.float32, torch.float64) \
+                or not x.is_contiguous() or x.device != st.device:
+            raise ValueError(f"score_rows: rows must be contiguous float32 / float64 [n, {dims.d_in}] on the "
+                             "detector's device")
+        if (sc is None) != (fl is None) or (sc is None and la is None) or (sc is None) != (st.kind == 0):
+            raise ValueError("score_rows: a scoring item needs scores and flags, a latents-only item neither")
+        if sc is not None and (sc.dtype != torch.float64 or sc.numel() != n or not sc.is_contiguous()
+                               or fl.dtype != torch.uint8 or fl.numel() != n or not fl.is_contiguous()):
+            raise ValueError("score_rows: scores must be float64 [n] and flags uint8 [n], contiguous")
+        if la is not None and (la.dtype != torch.float32 or tuple(la.shape) != (n, dims.latent)
+                               or not la.is_contiguous()):
+            raise ValueError(f"score_rows: latents must be contiguous float32 [n, {dims.latent}]")
+        if n == 0:
+            continue
+        r0 = np.arange(0, n, rpb, dtype=np.int64)
+        d = np.zeros(len(r0), dtype=SCORE_DTYPE)
+        esz = 8 if x.dtype == torch.float64 else 4
+        d["params"] = st.params.data_ptr()
+        d["raw"] = x.data_ptr() + esz * dims.d_in * r0
+        d["sc_a"] = st.scaler.data_ptr()
+        d["sc_b"] = st.scaler.data_ptr() + 8 * dims.d_in
+        if st.zscaler is not None:
+            d["z_mean"] = st.zscaler.data_ptr()
+            d["z_scale"] = st.zscaler.data_ptr() + 8 * dims.latent
+        if sc is not None:
+            d["score"] = sc.data_ptr() + 8 * r0
+            d["flag"] = fl.data_ptr() + r0
+        if la is not None:
+            d["lat"] = la.data_ptr() + 4 * dims.latent * r0
+        d["alarms"] = alarms.data_ptr() + 4 * i
+        d["threshold"] = st.threshold
+        d["nrows"] = np.minimum(rpb, n - r0)
+        d["d_in"], d["hidden"], d["latent"] = dims.d_in, dims.hidden, dims.latent
+        d["flags"] = (SCORE_RAW_F64 if esz == 8 else 0) | (SCORE_MINMAX if st.minmax else 0) | st.kind
+        d["score_scale"] = np.float32(1.0 / dims.d_in)
+        parts.append(d)
+    return np.concatenate(parts) if parts else np.zeros(0, dtype=SCORE_DTYPE)
+
+
+def score_rows(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], want_latents: bool = False,
+               rows_per_block: Optional[int] = None):
+    """Score raw rows with deployed detectors in one launch.  Returns per item
+    (scores float64 [n] or None, flags uint8 [n] or None, latents float32
+    [n, latent] or None) on the device and the int32 alarm counters (one per
+    item; valid after the stream is synchronised).  A latents-only state
+    (kind 0) always returns its latents."""
+    dev = states[0].device
+    rt = runtime(dev)
+    alarms = torch.zeros(len(states), dtype=torch.int32, device=dev)
+    scores, flags, lats = [], [], []
+    for st, x in zip(states, rows):
+        n = int(x.shape[0])
+        scoring = st.kind != 0
+        scores.append(torch.empty(n, dtype=torch.float64, device=dev) if scoring else None)
+        flags.append(torch.empty(n, dtype=torch.uint8, device=dev) if scoring else None)
+        lats.append(torch.empty(n, st.dims.latent, dtype=torch.float32, device=dev)
+                    if (want_latents or not scoring) else None)
+    desc = score_desc(states, rows, scores, flags, lats, alarms, rows_per_block)
+    if len(desc):
+        (dptr,) = rt.desc.put(desc)
+        _check(lib().fedmx_score_rows(dptr, len(desc), rt.stream), "fedmx_score_rows")
+    return list(zip(scores, flags, lats)), alarms
+
+
+def launch_score_rows(desc_dev: torch.Tensor, n: int, device):
+    _check(lib().fedmx_score_rows(desc_dev.data_ptr(), n, _stream(device)), "fedmx_score_rows")
 
 
 def launch_cen(desc_dev: torch.Tensor, n: int, device):

@@ -189,8 +189,94 @@ def scorer_timings(eng, clients, args) -> dict:
     return out
 
 
+def score_rows_timings(args) -> dict:
+    """``--score-rows``: score_rows_kernel (fedmx_score.hip) over ``--score-n``
+    synthetic N-BaIoT-shaped raw float64 rows for one detector, AE and CEN,
+    beside the same result composed from the ops that existed before it: host
+    ``transform`` + ``pad_features`` + host-to-device copy + ``forward_rows``
+    (+ ``cen_scores``, which refits the latent scaler per launch).  The fused
+    launch is event-timed with the raw rows already on the device; both paths
+    are also wall-clocked from host rows to host scores (alternating, so they
+    see the same machine state).  Phase split of the fused kernel: the same
+    launch with nothing but standardise + forward (latents only), and the
+    forward alone on prepared fp32 rows."""
+    from fedmse_decentralized_amd.data.scaler import StandardScaler
+    from fedmse_decentralized_amd.deploy.detector import Detector
+    from fedmse_decentralized_amd.engine.base import pad_features
+
+    dev = torch.device("cuda", 0)
+    dims = DEFAULT_DIMS
+    n = args.score_n
+    raws = generate_federation(SyntheticSpec(kind="nbaiot", n_clients=1, seed=1))
+    clients, _ = prepare_federation(raws, 1234)
+    sc = dict(clients[0].meta["scaler"])
+    kind = sc.pop("kind")
+    pool = np.concatenate([raws[0].normal, raws[0].abnormal, raws[0].test_normal], 0)
+    rows = pool[np.random.default_rng(3).integers(0, pool.shape[0], size=n)].copy()
+    init, _ = init_client_params(1, 0)
+    eng = HipEngine(dims, dev)
+    ae = Detector(dims=dims, model_type="autoencoder", params=init[0].numpy(), scaler_kind=kind, scaler=sc,
+                  threshold=0.5)
+    params = ae.padded_params().unsqueeze(0).to(dev)
+    train = torch.from_numpy(pad_features(clients[0].train)).to(dev)
+    _, tl = eng.forward_rows(params, [(0, train)], False, True)
+    zs = StandardScaler().fit(eng.fetch([tl[0]])[0])
+    cen = Detector(dims=dims, model_type="hybrid", params=ae.params, scaler_kind=kind, scaler=sc, threshold=1.0,
+                   latent_scorer="cen", latent_mean=zs.mean_, latent_scale=zs.scale_)
+    rows_dev = torch.from_numpy(rows).to(dev)
+    rpb = _hip.score_rows_per_block(n)
+    out = {"score_rows_n": n, "score_rows_per_block": rpb, "score_rows_workgroups": -(-n // rpb),
+           "score_rows_threads": 256, "score_rows_input": "float64"}
+    proc = ae.processor()
+    reps = max(args.reps // 2, 5)
+
+    def composed(det):
+        x = torch.from_numpy(pad_features(proc.transform(rows)[0])).to(dev)
+        if det.model_type == "autoencoder":
+            sse, _ = eng.forward_rows(params, [(0, x)], True, False)
+            return eng.fetch([sse[0]])[0]
+        _, lat = eng.forward_rows(params, [(0, train), (0, x)], False, True)
+        return eng.fetch([eng.cen_scores([lat[0]], [lat[1]])[0]])[0]
+
+    for name, det in (("ae", ae), ("cen", cen)):
+        state, _ = eng._score_state(det)
+        us = timeit(lambda: _hip.score_rows([state], [rows_dev]), reps=args.reps)[0]
+        out[f"score_rows_{name}_us"] = us
+        out[f"score_rows_{name}_rows_per_s"] = n / us * 1e6
+        wall = {"fused": [], "composed": []}
+        for i in range(reps + 1):
+            for path, fn in (("fused", lambda: eng.score_rows([det], [rows])), ("composed", lambda: composed(det))):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if i:   # (the first pass warms both paths up)
+                    wall[path].append(time.perf_counter() - t0)
+        for path, ts in wall.items():
+            out[f"{path}_{name}_host_to_host_ms"] = float(np.median(ts)) * 1e3
+            out[f"{path}_{name}_host_to_host_rows_per_s"] = n / float(np.median(ts))
+    # the composed chain's device part alone (rows already standardised, padded and copied)
+    x = torch.from_numpy(pad_features(proc.transform(rows)[0])).to(dev)
+    t0 = time.perf_counter()
+    for _ in range(3):
+        pad_features(proc.transform(rows)[0])
+    out["composed_host_transform_pad_ms"] = (time.perf_counter() - t0) / 3 * 1e3
+    out["composed_fwd_sse_us"] = timeit(lambda: eng.forward_rows(params, [(0, x)], True, False), reps=args.reps)[0]
+    out["composed_fwd_lat_us"] = timeit(lambda: eng.forward_rows(params, [(0, x)], False, True), reps=args.reps)[0]
+    _, lat = eng.forward_rows(params, [(0, train), (0, x)], False, True)
+    out["composed_cen_us"] = timeit(lambda: eng.cen_scores([lat[0]], [lat[1]]), reps=args.reps)[0]
+    # phase split of the fused kernel: standardise + forward to latents, no score
+    lat_only = _hip.ScoreState(params[0].contiguous(), dims, sc["mean_"], sc["scale_"], kind == "minmax", 0, 0.0)
+    out["score_rows_latents_only_us"] = timeit(lambda: _hip.score_rows([lat_only], [rows_dev]), reps=args.reps)[0]
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--score-rows", action="store_true", help="only the deployed-detector scoring timings "
+                   "(score_rows_kernel over --score-n raw rows, AE and CEN, beside the chain composed from "
+                   "transform + pad + copy + forward_rows + cen_scores)")
+    p.add_argument("--score-n", type=int, default=1_000_000)
     p.add_argument("--latent-scorer", action="store_true", help="only the latent-scorer timings (knn_score_kernel "
                    "beside cen_score_kernel, the evaluation chain and ms / round under either scorer)")
     p.add_argument("--scorer-rounds", type=int, default=200)
@@ -203,6 +289,10 @@ def main():
     p.add_argument("--reps", type=int, default=20)
     p.add_argument("--train-only", action="store_true", help="only the training-kernel timings (A/B of builds)")
     args = p.parse_args()
+    if args.score_rows:
+        out = score_rows_timings(args)
+        print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
+        return
     dev = torch.device("cuda", 0)
     raws = generate_federation(SyntheticSpec(kind="nbaiot", n_clients=args.clients, seed=1))
     clients, dev_set = prepare_federation(raws, 1234)
