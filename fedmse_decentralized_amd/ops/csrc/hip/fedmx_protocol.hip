@@ -58,6 +58,13 @@ struct ElectArgs {
 static_assert(sizeof(ElectArgs) == 120, "ElectArgs layout is shared with Python");
 constexpr int32_t ELECT_TRAIN_FAILED = -3;
 
+// The ballot's order (protocol/election.py::_ballot): ascending, a NaN score
+// after every number; equal scores (and NaN among NaN) keep selection order,
+// which the scans below get by replacing the running best only on `before`.
+__device__ __forceinline__ bool score_before(double s, double best) {
+  return s < best || (best != best && s == s);
+}
+
 __device__ __forceinline__ int train_failed(const ElectArgs& E) {
   int f = 0;
   if (E.err != nullptr)
@@ -125,13 +132,14 @@ __global__ __launch_bounds__(256) void elect_wsum_kernel(const ElectArgs E, cons
         }
         if (E.mode & 2) cand = cand && (sc <= E.vote_cap);
         // the serial scan of the reference loop over the candidates' lanes
-        // (uniform across the wave; NaN scores behave exactly as there)
+        // (uniform across the wave; a NaN score is voted for only when no
+        // eligible candidate has a number, as in the host ballot's sort)
         int best = -1;
         double best_s = 0.0;
         for (int ci = 0; ci < k; ++ci) {
           const double s_ci = __shfl(sc, ci, 64);
           const int ok_ci = __shfl(cand ? 1 : 0, ci, 64);
-          if (ok_ci && (best < 0 || s_ci < best_s)) {
+          if (ok_ci && (best < 0 || score_before(s_ci, best_s))) {
             best = ci;
             best_s = s_ci;
           }
@@ -217,7 +225,8 @@ __global__ __launch_bounds__(256) void elect_wsum_kernel(const ElectArgs E, cons
         if (c == v) continue;
         const double f = 1.0 + (u[j++] - 0.5) * 0.0002;
         const double sc = E.vec[(size_t)(E.rec != nullptr ? E.rec[ci] : c) * 4] * f;
-        if (E.agg_counts[c] < E.cap && (!(E.mode & 2) || sc <= E.vote_cap) && (best < 0 || sc < best_s)) {
+        if (E.agg_counts[c] < E.cap && (!(E.mode & 2) || sc <= E.vote_cap) &&
+            (best < 0 || score_before(sc, best_s))) {
           best = c;
           best_ci = ci;
           best_s = sc;

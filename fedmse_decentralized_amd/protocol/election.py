@@ -14,6 +14,14 @@
 Scores arrive from the engine as the noise-free per-client MSE (identical on
 every rank after the score all-reduce); only the noise is drawn here.
 
+Order of a ballot: ascending by noisy score, a NaN score (a diverged client)
+after every number, equal scores and NaN among NaN in selection order.  A
+plain ``sort`` on floats leaves NaN wherever its comparisons happen to put it,
+so the rule is spelled out in the sort key; for scores without NaN it is the
+reference's order.  The device election (``elect_wsum_kernel``, both its
+wave and its serial path) applies the same rule, so a diverged client cannot
+make the device round and the host path elect different aggregators.
+
 Variants (``ExperimentConfig.election`` / ``protocol_variant``):
 
 * ``elect_majority`` — the legacy centralised ``GlobalAggregator.select_aggregator``
@@ -62,7 +70,8 @@ def _ballot(voter: int, selected: Sequence[int], base_scores: Dict[int, float], 
         noisy.append((cid, s))
         if log_enabled:
             log.info(f"[Client {voter}] Client {list(selected).index(cid) + 1} MSE score: {s:.6f}")
-    noisy.sort(key=lambda t: t[1])
+    # NaN after every number; the stable sort keeps selection order among equals
+    noisy.sort(key=lambda t: (1, 0.0) if t[1] != t[1] else (0, t[1]))
     for cid, s in noisy:
         if vote_mse_cap is not None and not (s <= vote_mse_cap):
             continue
