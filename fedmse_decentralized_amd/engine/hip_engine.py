@@ -155,11 +155,49 @@ class HipEngine(Engine):
         out = self.fetch([_hip.auc(list(scores), list(labels))])[0]
         return self._auc_fixup(out, scores, labels)
 
-    def _auc_fixup(self, out, scores, labels):
-        for i in np.flatnonzero(out == -1.0):   # class too large for the LDS sort: exact host path
-            s = scores[i].detach().double().cpu().numpy()
-            out[i] = _host.roc_auc(np.nan_to_num(s), labels[i].cpu().numpy())
+    def _auc_fixup(self, out, scores, labels, f32_scale: float = 1.0):
+        """Entries ``auc_kernel`` answered -1 (class too large for its LDS
+        sort): recomputed by the multi-workgroup path (one more launch
+        sequence and fetch), read with the same ``f32_scale``; a pair beyond
+        its 2^26 rows keeps the exact host path."""
+        bad = np.flatnonzero(out == -1.0)
+        big = [i for i in bad if int(scores[i].shape[0]) <= _hip.AUC_LARGE_MAX_ROWS]
+        if big:
+            vals = self.fetch([_hip.auc_large([scores[i].detach().contiguous() for i in big],
+                                              [labels[i] for i in big], f32_scale)])[0]
+            out[big] = vals
+        for i in bad:
+            if int(scores[i].shape[0]) > _hip.AUC_LARGE_MAX_ROWS:
+                s = scores[i].detach().double().cpu().numpy()
+                out[i] = _host.roc_auc(np.nan_to_num(s), labels[i].cpu().numpy())
         return out
+
+    def _auc_large_plan(self, scores, labels, f32_scale: float, aucs_buf) -> Optional[dict]:
+        """The large-path part of an AUC plan: the clients whose smaller test
+        class is beyond ``auc_kernel``'s LDS sort (the labels are fixed, so the
+        classes are counted once, here), their descriptors, one workspace and
+        the launch's grid.  None when no client is large: nothing is allocated
+        and nothing more is launched."""
+        st = self.store
+        big, m, npr = [], [], []
+        for c in range(len(scores)):
+            y = st.labels(c)
+            P = int(np.count_nonzero(y))
+            N = int(y.shape[0]) - P
+            if min(P, N) > _hip.AUC_MAX_SORT and P + N <= _hip.AUC_LARGE_MAX_ROWS:
+                big.append(c)
+                m.append(min(P, N))
+                npr.append(max(P, N))
+        if not big:
+            return None
+        rows = [m[i] + npr[i] for i in range(len(big))]
+        ws = torch.empty(sum(rows), dtype=torch.float64, device=self.device)
+        ctr = torch.zeros(_hip.AUC_LARGE_CTR_WORDS * len(big), dtype=torch.int64, device=self.device)
+        desc = _hip.auc_large_desc([scores[c] for c in big], [labels[c] for c in big], aucs_buf.dev_ptr,
+                                   ws.data_ptr(), ctr.data_ptr(), f32_scale, out_index=big)
+        chunks, slices = _hip.auc_large_grid(m, npr)
+        return dict(clients=big, desc=torch.from_numpy(desc.view(np.uint8).copy()).to(self.device), ws=ws, ctr=ctr,
+                    max_rows=max(rows), chunks=chunks, slices=slices)
 
     def store_device(self) -> torch.device:
         """The device with its index, as tensors moved to ``self.device`` report it."""
@@ -308,17 +346,22 @@ class HipEngine(Engine):
             scores_all = torch.empty(sum(int(st.test_off[c + 1] - st.test_off[c]) for c in range(C)),
                                      dtype=torch.float64, device=self.device)
             blob, launch, scores = self._scorer_plan(lat[0::2], lat[1::2], scores_all)
-            adesc = _hip.auc_desc(scores, labels, aucs_buf.dev_ptr, 1.0)
+            scale = 1.0
             p = dict(fwd=fwd, scorer=blob, score_launch=launch, scores=scores, test_lat=lat[1::2])
         elif model_type == "autoencoder":
             fwd = _hip.FwdPlan(params, [(c, st.rows("test", c)) for c in range(C)], self.dims,
                                want_sse=True, want_latent=False)
             scores = fwd.sse_views()
-            adesc = _hip.auc_desc(scores, labels, aucs_buf.dev_ptr, 1.0 / self.dims.d_in)
+            scale = 1.0 / self.dims.d_in
             p = dict(fwd=fwd, scorer=None, score_launch=None, scores=scores, test_lat=None)
         else:
             raise ValueError(f"unknown model_type {model_type!r}")
+        adesc = _hip.auc_desc(scores, labels, aucs_buf.dev_ptr, scale)
         p["auc"] = torch.from_numpy(adesc.view(np.uint8).copy()).to(self.device)
+        # clients beyond auc_kernel's LDS sort: the multi-workgroup path after it, on the
+        # same stream, overwrites their -1 in aucs_buf (None: no such client, nothing added)
+        p["auc_large"] = self._auc_large_plan(scores, labels, scale, aucs_buf)
+        p["auc_scale"] = scale
         p["aucs"] = aucs
         p["aucs_buf"] = aucs_buf
         p["labels"] = labels
@@ -407,6 +450,10 @@ class HipEngine(Engine):
             _hip.launch_detect(p["detect"], self.store.num_clients, self.device)
         else:
             _hip.launch_auc(p["auc"], self.store.num_clients, self.device)
+            big = p["auc_large"]
+            if big is not None:
+                _hip.launch_auc_large(big["desc"], len(big["clients"]), big["max_rows"], big["chunks"], big["slices"],
+                                      self.device)
         return p["aucs"]
 
     def detect_metrics(self, calib, scores, labels, ranks, calib_labels=None, score_scale=1.0, value="f1"):
@@ -430,7 +477,7 @@ class HipEngine(Engine):
             return evaluate_clients(self, list(range(self.store.num_clients)), model_type, metric, keep_latents)
         aucs = self.evaluate_launch(model_type)
         p = self._plan(model_type)
-        vals = self._auc_fixup(self.fetch([aucs])[0], p["scores"], p["labels"])
+        vals = self._auc_fixup(self.fetch([aucs])[0], p["scores"], p["labels"], p["auc_scale"])
         return EvalResult(np.asarray(vals, dtype=np.float64), {}, self._plan_latents(p, keep_latents))
 
     def _plan_latents(self, p: dict, keep_latents: bool):

@@ -81,6 +81,46 @@ def roc_auc(labels, scores) -> float:
     return _host.roc_auc(s, np.asarray(labels))
 
 
+def read_scores(scores, f32_scale: float = 1.0) -> np.ndarray:
+    """Scores as the AUC kernels read them: a float32 score times
+    ``f32_scale`` in float32, then widened; a float64 score as is; then
+    NaN -> 0 and +-inf -> +-DBL_MAX (``numpy.nan_to_num``)."""
+    s = np.asarray(scores)
+    if s.dtype == np.float32:
+        s = (s * np.float32(f32_scale)).astype(np.float64)
+    else:
+        s = s.astype(np.float64)
+    return np.nan_to_num(s)
+
+
+def auc_chunked_numpy(scores, labels, chunk_keys: int, f32_scale: float = 1.0) -> float:
+    """The rule of the multi-workgroup device AUC (README "Exact AUC at any
+    size", fedmx_auc_large.hip) written out: the smaller class (the positives
+    on a tie) is cut into chunks of ``chunk_keys`` values, each chunk is
+    sorted, every value of the other class is searched in it, and the counts
+    of smaller and of equal values are summed as integers.  Equal to
+    ``_host.roc_auc`` of the read scores to the bit while P*N < 2^52."""
+    s = read_scores(scores, f32_scale)
+    pos = np.asarray(labels) != 0
+    P = int(pos.sum())
+    N = int(s.shape[0]) - P
+    if P == 0 or N == 0:
+        return float("nan")
+    sort_pos = P <= N
+    keys, probe = (s[pos], s[~pos]) if sort_pos else (s[~pos], s[pos])
+    less = eq = 0
+    for k0 in range(0, keys.shape[0], int(chunk_keys)):
+        chunk = np.sort(keys[k0:k0 + int(chunk_keys)])
+        lb = np.searchsorted(chunk, probe, side="left")
+        ub = np.searchsorted(chunk, probe, side="right")
+        less += int(lb.sum(dtype=np.int64))
+        eq += int((ub - lb).sum(dtype=np.int64))
+    pairs = float(P) * float(N)
+    if sort_pos:
+        return (pairs - float(less) - 0.5 * float(eq)) / pairs
+    return (float(less) + 0.5 * float(eq)) / pairs
+
+
 def classification_metrics(labels, scores, threshold: float = 0.5):
     y = np.asarray(labels).astype(np.int64)
     pred = (np.asarray(scores) > threshold).astype(np.int64)

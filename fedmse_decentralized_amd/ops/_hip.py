@@ -71,6 +71,16 @@ AUC_DTYPE = np.dtype([
     ("score", "<u8"), ("label", "<u8"), ("out", "<u8"),
     ("n", "<i4"), ("score_is_f64", "<i4"), ("score_scale", "<f4"), ("pad", "<i4"),
 ])
+# fedmx_auc_large.hip AucLargeDesc
+AUC_LARGE_DTYPE = np.dtype([
+    ("score", "<u8"), ("label", "<u8"), ("out", "<u8"), ("ws", "<u8"), ("ctr", "<u8"),
+    ("n", "<i4"), ("score_is_f64", "<i4"), ("score_scale", "<f4"), ("pad", "<i4"),
+])
+AUC_MAX_SORT = 8192              # keys auc_kernel sorts in LDS; a larger smaller class takes the large path
+AUC_LARGE_CTR_WORDS = 8          # u64 counters per descriptor (one 64-byte line)
+AUC_LARGE_SLICE_MIN_ROWS = 1024  # a descriptor takes at most ceil(probe rows / this) slices
+AUC_LARGE_MAX_ROWS = 1 << 26     # rows per (scores, labels) pair the large path accepts
+AUC_LARGE_RESIDENT = 2 * 256     # pairs workgroups resident at once (1024 threads, 64 KB of LDS: 2 per CU, 256 CUs)
 SEG_DTYPE = np.dtype([("sse", "<u8"), ("n", "<i4"), ("batch", "<i4"), ("out", "<u8")])
 # fedmx_detect.hip DetectDesc
 DETECT_DTYPE = np.dtype([
@@ -196,6 +206,7 @@ def lib():
                 "fedmx_knn_tile_rows": [],
                 "fedmx_knn_max_k": [],
                 "fedmx_auc": [vp, i32, vp],
+                "fedmx_auc_large": [vp, i32, i32, i32, i32, i32, vp],
                 "fedmx_detect": [vp, i32, vp],
                 "fedmx_score_rows": [vp, i32, vp],
                 "fedmx_score_chunk_rows": [],
@@ -232,6 +243,10 @@ def lib():
             assert L.fedmx_cen_desc_size() == CEN_DTYPE.itemsize
             assert L.fedmx_knn_desc_size() == KNN_DTYPE.itemsize
             assert L.fedmx_auc_desc_size() == AUC_DTYPE.itemsize
+            assert L.fedmx_auc_large_desc_size() == AUC_LARGE_DTYPE.itemsize
+            assert L.fedmx_auc_large_ctr_words() == AUC_LARGE_CTR_WORDS
+            assert L.fedmx_auc_large_slice_min_rows() == AUC_LARGE_SLICE_MIN_ROWS
+            assert L.fedmx_auc_large_max_rows() == AUC_LARGE_MAX_ROWS
             assert L.fedmx_detect_desc_size() == DETECT_DTYPE.itemsize
             assert L.fedmx_score_desc_size() == SCORE_DTYPE.itemsize
             assert L.fedmx_score_chunk_rows() == SCORE_CHUNK_ROWS
@@ -357,7 +372,7 @@ class use_runtime:
 
 class on_stream:
     """Route the cached-plan launches (FwdPlan.run, launch_cen / launch_auc /
-    launch_score_reduce, copy kernels) to another HIP stream (a
+    launch_auc_large / launch_score_reduce, copy kernels) to another HIP stream (a
     ``torch.cuda.Stream``), e.g. evaluation overlapping the next round's
     training; torch work inside the block follows the same stream."""
 
@@ -689,9 +704,111 @@ def auc(scores: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], f32_scal
     return view
 
 
-def _score_vec(t: torch.Tensor, what: str) -> int:
+def _check_chunk_keys(chunk_keys: int) -> int:
+    ck = int(chunk_keys)
+    if ck < 64 or ck > AUC_MAX_SORT or ck & (ck - 1):
+        raise ValueError(f"auc_large: chunk_keys must be a power of two from 64 to {AUC_MAX_SORT}, got {chunk_keys!r}")
+    return ck
+
+
+def auc_large_grid(sort_rows, probe_rows, chunk_keys: int = AUC_MAX_SORT,
+                   resident: int = AUC_LARGE_RESIDENT) -> Tuple[int, int]:
+    """(chunks, slices) of one pairs launch (fedmx_auc_large.hip) over
+    descriptors whose sort class has ``sort_rows[i]`` rows and whose probe
+    class ``probe_rows[i]``: the chunk count of the largest sort class, and
+    as many probe slices as fill the chip's resident workgroups once, but no
+    more than the largest probe class gives 1024 rows each.  Upper bounds of
+    the class sizes do as well: workgroups beyond a descriptor's own chunk
+    and slice counts leave at once."""
+    ck = _check_chunk_keys(chunk_keys)
+    sort_rows = np.atleast_1d(np.asarray(sort_rows, dtype=np.int64))
+    probe_rows = np.atleast_1d(np.asarray(probe_rows, dtype=np.int64))
+    if sort_rows.shape != probe_rows.shape:
+        raise ValueError("auc_large: one sort and one probe size per descriptor")
+    live = (sort_rows > 0) & (probe_rows > 0)
+    if not live.any():
+        return 0, 1
+    nch = -(-sort_rows[live] // ck)
+    chunks = int(nch.max())
+    want = -(-int(resident) // int(nch.sum()))
+    cap = -(-int(probe_rows[live].max()) // AUC_LARGE_SLICE_MIN_ROWS)
+    return chunks, int(max(1, min(want, cap, 65535)))
+
+
+def auc_large_cover(sort_rows: int, probe_rows: int, chunk_keys: int, slices: int):
+    """The work of every pairs workgroup that stays, as the kernel cuts it for
+    one descriptor inside a launch with ``slices`` slices: a list of
+    ((first key, end key), (first probe row, end probe row))."""
+    ck = _check_chunk_keys(chunk_keys)
+    m, npr = int(sort_rows), int(probe_rows)
+    if m <= 0 or npr <= 0:
+        return []
+    nchunks = -(-m // ck)
+    nsl = min(max(-(-npr // AUC_LARGE_SLICE_MIN_ROWS), 1), int(slices))
+    return [((c * ck, min(m, (c + 1) * ck)), ((npr * s) // nsl, (npr * (s + 1)) // nsl))
+            for c in range(nchunks) for s in range(nsl)]
+
+
+def auc_large_desc(scores, labels, out_ptr: int, ws_ptr: int, ctr_ptr: int, f32_scale: float = 1.0,
+                   out_index: Optional[Sequence[int]] = None) -> np.ndarray:
+    """AucLargeDesc array (fedmx_auc_large.hip): item i's result goes to
+    float64 slot ``out_index[i]`` (default i) of ``out_ptr``; its workspace is
+    the next ``n`` doubles of ``ws_ptr`` (sum of all n in total) and its
+    counters the i-th 64 bytes of ``ctr_ptr``, zero before the first launch."""
+    n = len(scores)
+    desc = np.zeros(n, dtype=AUC_LARGE_DTYPE)
+    off = 0
+    for i, (s, l) in enumerate(zip(scores, labels)):
+        if l.dtype != torch.int32 or l.dim() != 1 or not l.is_contiguous() or l.shape[0] != s.shape[0]:
+            raise ValueError("auc_large: labels must be contiguous int32, one per score")
+        f64 = _score_vec(s, "scores", "auc_large")
+        rows = int(s.shape[0])
+        if rows > AUC_LARGE_MAX_ROWS:
+            raise ValueError(f"auc_large: {rows} rows are beyond the {AUC_LARGE_MAX_ROWS} a pair may have")
+        desc[i]["score"] = s.data_ptr()
+        desc[i]["label"] = l.data_ptr()
+        desc[i]["out"] = out_ptr + 8 * (i if out_index is None else int(out_index[i]))
+        desc[i]["ws"] = ws_ptr + 8 * off
+        desc[i]["ctr"] = ctr_ptr + 8 * AUC_LARGE_CTR_WORDS * i
+        desc[i]["n"] = rows
+        desc[i]["score_is_f64"] = f64
+        desc[i]["score_scale"] = f32_scale
+        off += rows
+    return desc
+
+
+def auc_large(scores: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], f32_scale: float = 1.0,
+              chunk_keys: int = AUC_MAX_SORT) -> np.ndarray:
+    """Exact tie-aware ROC-AUC per (scores, labels) pair by the
+    multi-workgroup path, whatever the class sizes (up to 2^26 rows a pair;
+    more raise ValueError).  Returns a float64 host view written by the
+    kernels (valid after ``runtime(dev).sync()``); NaN where a class is empty."""
+    ck = _check_chunk_keys(chunk_keys)
+    dev = scores[0].device
+    rt = runtime(dev)
+    k = len(scores)
+    rows = np.array([int(s.shape[0]) for s in scores], dtype=np.int64)
+    # workspace and counters from torch's pool: freed on return, reused in stream order
+    ws = torch.empty(max(int(rows.sum()), 1), dtype=torch.float64, device=dev)
+    ctr = torch.zeros(AUC_LARGE_CTR_WORDS * k, dtype=torch.int64, device=dev)
+    optr, view = rt.out.take(np.float64, k)
+    desc = auc_large_desc(scores, labels, optr, ws.data_ptr(), ctr.data_ptr(), f32_scale)
+    # the class sizes are known on the device only: the smaller class has at most half the rows
+    chunks, slices = auc_large_grid(rows // 2, rows, ck)
+    (dptr,) = rt.desc.put(desc)
+    _check(lib().fedmx_auc_large(dptr, k, int(rows.max()), chunks, slices, ck, rt.stream), "fedmx_auc_large")
+    return view
+
+
+def launch_auc_large(desc_dev: torch.Tensor, n: int, max_rows: int, chunks: int, slices: int, device,
+                     chunk_keys: int = AUC_MAX_SORT):
+    _check(lib().fedmx_auc_large(desc_dev.data_ptr(), n, int(max_rows), int(chunks), int(slices),
+                                 _check_chunk_keys(chunk_keys), _stream(device)), "fedmx_auc_large")
+
+
+def _score_vec(t: torch.Tensor, what: str, who: str = "detect") -> int:
     if t.dtype not in (torch.float32, torch.float64) or t.dim() != 1 or not t.is_contiguous():
-        raise ValueError(f"detect: {what} must be a contiguous float32 or float64 vector")
+        raise ValueError(f"{who}: {what} must be a contiguous float32 or float64 vector")
     return 1 if t.dtype == torch.float64 else 0
 
 

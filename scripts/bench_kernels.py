@@ -271,8 +271,71 @@ def score_rows_timings(args) -> dict:
     return out
 
 
+def auc_large_timings(args) -> dict:
+    """``--auc-large``: the multi-workgroup AUC path (fedmx_auc_large.hip)
+    beside the host fallback it replaces, on the same tensors.  Per shape:
+    ``*_launch_us`` the cached-plan launch sequence (events), ``*_call_us``
+    ``_hip.auc_large`` with its workspace from torch's pool (events),
+    ``*_engine_ms`` ``engine.auc`` as a round pays it (wall clock: auc_kernel's
+    -1, a fetch, the large path, a second fetch) and ``*_host_ms`` the fallback
+    it replaces (wall clock: auc_kernel's -1, a fetch, the D2H copy of the
+    scores and ``_host.roc_auc``)."""
+    from fedmse_decentralized_amd.ops import _host
+
+    dev = torch.device("cuda", 0)
+    eng = HipEngine(DEFAULT_DIMS, dev)
+    g = torch.Generator(device="cpu").manual_seed(5)
+    shapes = {"10k_in_100k": [(10_000, 90_000)], "100k_100k": [(100_000, 100_000)],
+              "1m_1m": [(1_000_000, 1_000_000)], "10x_9k_10k": [(9_000, 10_000)] * 10}
+    out = {}
+
+    def wall(fn, reps):
+        fn()
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts))
+
+    def host_fallback(scores, labels):
+        vals = eng.fetch([_hip.auc(scores, labels)])[0]
+        for i in np.flatnonzero(vals == -1.0):
+            s = scores[i].detach().double().cpu().numpy()
+            vals[i] = _host.roc_auc(np.nan_to_num(s), labels[i].cpu().numpy())
+        return vals
+
+    for name, pairs in shapes.items():
+        scores, labels = [], []
+        for P, N in pairs:
+            y = torch.cat([torch.ones(P, dtype=torch.int32), torch.zeros(N, dtype=torch.int32)])
+            y = y[torch.randperm(P + N, generator=g)]
+            s = torch.rand(P + N, dtype=torch.float64, generator=g) + 0.2 * y
+            scores.append(s.to(dev))
+            labels.append(y.to(dev))
+        rows = [P + N for P, N in pairs]
+        ws = torch.empty(sum(rows), dtype=torch.float64, device=dev)
+        ctr = torch.zeros(_hip.AUC_LARGE_CTR_WORDS * len(pairs), dtype=torch.int64, device=dev)
+        res = torch.zeros(len(pairs), dtype=torch.float64, device=dev)
+        desc = _hip.auc_large_desc(scores, labels, res.data_ptr(), ws.data_ptr(), ctr.data_ptr())
+        blob = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+        chunks, slices = _hip.auc_large_grid([min(p) for p in pairs], [max(p) for p in pairs])
+        out[f"{name}_grid"] = [chunks, slices]
+        out[f"{name}_launch_us"] = timeit(lambda: _hip.launch_auc_large(blob, len(pairs), max(rows), chunks, slices,
+                                                                        dev), reps=args.reps)[0]
+        out[f"{name}_call_us"] = timeit(lambda: _hip.auc_large(scores, labels), reps=args.reps)[0]
+        out[f"{name}_engine_ms"] = wall(lambda: eng.auc(scores, labels), args.reps)
+        out[f"{name}_host_ms"] = wall(lambda: host_fallback(scores, labels), max(3, args.reps // 4))
+        new, old = eng.auc(scores, labels), host_fallback(scores, labels)
+        out[f"{name}_equal_bits"] = bool(np.array_equal(new, old)) and bool(np.array_equal(res.cpu().numpy(), old))
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--auc-large", action="store_true", help="only the large-class AUC timings (the multi-workgroup "
+                   "path beside the host fallback it replaces)")
     p.add_argument("--score-rows", action="store_true", help="only the deployed-detector scoring timings "
                    "(score_rows_kernel over --score-n raw rows, AE and CEN, beside the chain composed from "
                    "transform + pad + copy + forward_rows + cen_scores)")
@@ -289,8 +352,8 @@ def main():
     p.add_argument("--reps", type=int, default=20)
     p.add_argument("--train-only", action="store_true", help="only the training-kernel timings (A/B of builds)")
     args = p.parse_args()
-    if args.score_rows:
-        out = score_rows_timings(args)
+    if args.score_rows or args.auc_large:
+        out = (score_rows_timings if args.score_rows else auc_large_timings)(args)
         print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
         return
     dev = torch.device("cuda", 0)
