@@ -287,7 +287,10 @@ class Engine:
 
     def standardize_ddof1(self, x: torch.Tensor) -> torch.Tensor:
         """(x - mean) / (std_ddof1 + 1e-8) over the real D columns
-        (`src/Trainer/client_trainer.py:220-223`)."""
+        (`src/Trainer/client_trainer.py:220-223`); the padded columns of the
+        result are 0.  A single row has no unbiased standard deviation:
+        ``torch.std`` gives NaN there, as in the reference, so every real
+        column of the result is NaN (and the padding still 0) on every engine."""
         raise NotImplementedError
 
     # -- round operations (defaults in terms of the primitives) -----------------

@@ -586,18 +586,42 @@ class FwdPlan:
         return [self.lat[o:o + n] for o, n in zip(self.offs, self.sizes)]
 
 
+def _cen_rows(t: torch.Tensor, latent: int, what: str):
+    # (the strides of a dimension of one element, or of a tensor without rows, are never applied)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < latent or (
+            t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"cen: {what} must be float32 [n, >= {latent}] with unit column stride")
+
+
 def cen_desc(train_lat, test_lat, out: torch.Tensor, latent: int) -> Tuple[np.ndarray, List[torch.Tensor]]:
+    """CenDesc array (fedmx_eval.hip): item i scores every row of
+    ``test_lat[i]`` against the scaler fitted on ``train_lat[i]`` into
+    consecutive float64 slots of ``out``.  The kernel reads both tensors of
+    an item with one row stride, so they must share it (equal-stride views of
+    wider buffers are fine; the stride of a tensor of at most one row is
+    never applied and not compared).  Raises ValueError otherwise, for a tensor with
+    fewer than ``latent`` columns or a column stride other than 1; nothing is
+    launched.  Returns (descriptors, per-item views of ``out``)."""
+    if len(train_lat) != len(test_lat):
+        raise ValueError("cen: one test set per train set")
     n = len(train_lat)
     desc = np.zeros(n, dtype=CEN_DTYPE)
     views, off = [], 0
     for i, (tr, te) in enumerate(zip(train_lat, test_lat)):
+        _cen_rows(tr, latent, "train latents")
+        _cen_rows(te, latent, "test latents")
+        # a tensor of at most one row is read at its first row only: its row stride is immaterial
+        strides = {int(t.stride(0)) for t in (tr, te) if t.shape[0] > 1}
+        if len(strides) > 1:
+            raise ValueError(f"cen: train and test latents of item {i} have row strides {tr.stride(0)} and "
+                             f"{te.stride(0)}; the kernel reads both with one")
         desc[i]["train_lat"] = tr.data_ptr()
         desc[i]["test_lat"] = te.data_ptr()
         desc[i]["out"] = out.data_ptr() + 8 * off
         desc[i]["n_train"] = tr.shape[0]
         desc[i]["n_test"] = te.shape[0]
         desc[i]["latent"] = latent
-        desc[i]["stride"] = tr.stride(0)
+        desc[i]["stride"] = strides.pop() if strides else tr.stride(0)
         views.append(out[off:off + te.shape[0]])
         off += te.shape[0]
     return desc, views

@@ -131,7 +131,8 @@ __global__ __launch_bounds__(256) void broadcast_rows_kernel(float* __restrict__
   if (dst1 != nullptr) reinterpret_cast<f32x4*>(dst1 + base)[i4] = v;
 }
 
-// (x - mean) / (std_unbiased + 1e-8) per real column.  Rows are staged in LDS
+// (x - mean) / (std_unbiased + 1e-8) per real column (NaN for a single row,
+// whose unbiased std is undefined; padded columns 0 always).  Rows are staged in LDS
 // in chunks of up to 256 rows (128 KB); 1024 threads = 8 row groups x 128
 // columns; column sums in float64, row groups combined in fixed order.
 constexpr int STD_CHUNK = 256;
@@ -184,7 +185,8 @@ __global__ __launch_bounds__(1024) void standardize_lds_kernel(const float* __re
     double qq = 0.0;
 #pragma unroll
     for (int g = 0; g < STD_GROUPS; ++g) qq += s_part[g][col];
-    const double var = qq / (n > 1 ? (n - 1) : 1);
+    // one row: the unbiased variance is 0 / 0, NaN as torch.std gives
+    const double var = n > 1 ? qq / (n - 1) : __builtin_nan("");
     s_mean[col] = (float)mean;
     s_den[col] = (float)sqrt(var) + 1e-8f;
   }

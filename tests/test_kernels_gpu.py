@@ -57,11 +57,15 @@ def test_forward_rows_matches_torch():
         torch.testing.assert_close(z.cpu().double(), rz, rtol=2e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("dims", [(46, 27, 7), (115, 20, 5), (120, 30, 10), (127, 27, 7)])
+@pytest.mark.parametrize("dims", [(46, 27, 7), (115, 20, 5), (120, 30, 10), (127, 27, 7),
+                                  # around the compact order's input columns 113 / 114 (one real, one
+                                  # padding; neither), and the first shape past each compact bound
+                                  (112, 27, 7), (113, 27, 7), (114, 27, 7), (116, 27, 7), (115, 28, 7), (115, 27, 8)])
 def test_forward_rows_other_shapes_match_torch(dims):
     """Shapes other than the reference's: the compact forward order (d_in <=
     115, hidden <= 27, latent <= 7) and the identity-order fallback (wider
-    models) both match the fp64 reference, SSE and latents."""
+    models) both match the fp64 reference, SSE and latents; row counts on
+    both sides of one 16-row tile and of one 64-row block."""
     from fedmse_decentralized_amd.models.layout import ModelDims
 
     md = ModelDims(*dims)
@@ -70,11 +74,11 @@ def test_forward_rows_other_shapes_match_torch(dims):
     pad = canonical_to_padded(params, md).to(DEV)
     g = torch.Generator().manual_seed(4)
     xs = []
-    for n in (5, 40, 257):
+    for n in (5, 40, 257, 15, 16, 17, 63, 64, 65):
         x = torch.zeros(n, 128)
         x[:, :md.d_in] = torch.randn(n, md.d_in, generator=g)
         xs.append(x.to(DEV))
-    items = [(0, xs[0]), (1, xs[1]), (0, xs[2])]
+    items = [(0, xs[0]), (1, xs[1]), (0, xs[2])] + [(i % 2, x) for i, x in enumerate(xs[3:])]
     sse, lat = _hip.forward_rows(pad, items, md, True, True)
     for (row, x), s, z in zip(items, sse, lat):
         rs, rz = rowwise_sse(params[row].double(), x[:, :md.d_in].cpu().double(), md)
