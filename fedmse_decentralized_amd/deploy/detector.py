@@ -278,18 +278,27 @@ def _ae_scores(sse: np.ndarray, d_in: int) -> np.ndarray:
         return (np.asarray(sse, dtype=np.float32) * np.float32(1.0 / d_in)).astype(np.float64)
 
 
-def cen_scores_stored(lat: np.ndarray, mean: np.ndarray, scale: np.ndarray) -> np.ndarray:
-    """cen_score_kernel's per-row loop under a stored scaler: per column
-    ``t0 = fp32((double)z - mean)``, ``t1 = fp32((double)t0 / scale)``, the
-    squares accumulated in float64 in column order from 0, then the root."""
+def cen_terms_stored(lat: np.ndarray, mean: np.ndarray, scale: np.ndarray) -> np.ndarray:
+    """The squares cen_score_kernel's per-row loop adds up, float64 [n, Z]:
+    per column ``t0 = fp32((double)z - mean)``, ``t1 = fp32((double)t0 /
+    scale)``, ``(double)t1 * (double)t1``."""
     with np.errstate(all="ignore"):
         t = np.asarray(lat, dtype=np.float32).copy()
         t -= mean          # numpy in-place: computed in float64, stored as float32
         t /= scale
         t64 = t.astype(np.float64)
-        acc = np.zeros(t64.shape[0], dtype=np.float64)
-        for j in range(t64.shape[1]):
-            acc += t64[:, j] * t64[:, j]
+        return t64 * t64
+
+
+def cen_scores_stored(lat: np.ndarray, mean: np.ndarray, scale: np.ndarray) -> np.ndarray:
+    """cen_score_kernel's per-row loop under a stored scaler: the terms of
+    ``cen_terms_stored`` accumulated in float64 in column order from 0, then
+    the root."""
+    with np.errstate(all="ignore"):
+        terms = cen_terms_stored(lat, mean, scale)
+        acc = np.zeros(terms.shape[0], dtype=np.float64)
+        for j in range(terms.shape[1]):
+            acc += terms[:, j]
         return np.sqrt(acc)
 
 
@@ -337,3 +346,138 @@ def score_rows_numpy(detector: Detector, rows: np.ndarray, engine=None, want_lat
             scores = engine.fetch([engine.knn_scores([tr], [lat[0]], det.knn_k)[0]])[0].astype(np.float64)
     out = clean_and_flag(scores, det.threshold)
     return out + (lat_np,) if want_latents else out
+
+
+# ---------------------------------------------------------------------------
+# explaining an alarm (README "Explaining an alarm")
+EXPLAIN_MAX_K = 16
+
+
+@dataclass
+class Explanation:
+    """What ``Engine.explain_rows`` returns per detector, as numpy arrays."""
+    rows: np.ndarray                        # int64 [m]: the explained indices into the raw rows
+    idx: np.ndarray                         # int32 [m, K]: features by falling squared residual; -1 unused
+    resid: np.ndarray                       # float32 [m, K]: y - x in standardised units; 0 unused
+    sse: np.ndarray                         # float32 [m]: forward_rows' per-row sum of squared residuals
+    resid_full: Optional[np.ndarray] = None     # float32 [m, D] (dense mode)
+    latent_terms: Optional[np.ndarray] = None   # float64 [m, Z] (hybrid + cen): score = sqrt(sum over j from 0)
+
+
+def check_top_k(top_k) -> int:
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= EXPLAIN_MAX_K:
+        raise ValueError(f"explain_rows: top_k must be an integer in 1..{EXPLAIN_MAX_K}, got {top_k!r}")
+    return int(top_k)
+
+
+def check_which(which, n: int) -> np.ndarray:
+    """The explained row indices as int64 [m]: ``which`` (any order, repeats
+    allowed, every entry in ``[0, n)``) or, for None, ``0..n-1``."""
+    if which is None:
+        return np.arange(n, dtype=np.int64)
+    if torch.is_tensor(which):
+        which = which.detach().cpu().numpy()
+    w = np.asarray(which)
+    if w.ndim != 1 or (w.size and w.dtype.kind not in "iu"):
+        raise ValueError(f"explain_rows: which must be a vector of row indices, got {w.dtype} {w.shape}")
+    w = w.astype(np.int64)
+    if w.size and (int(w.min()) < 0 or int(w.max()) >= n):
+        raise ValueError(f"explain_rows: which must lie in [0, {n})")
+    return w
+
+
+def select_top_k(resid: np.ndarray, top_k: int):
+    """The selection rule on fp32 residual rows [m, D] -> ``(idx int32 [m, K],
+    resid float32 [m, K])``: key ``fp32(r * r)`` with NaN ranked as +inf,
+    descending, equal keys by ascending feature; slots past ``min(K, D)``
+    hold -1 and 0."""
+    k = check_top_k(top_k)
+    r = np.asarray(resid, dtype=np.float32)
+    if r.ndim != 2:
+        raise ValueError(f"residual rows must be [m, D], got {r.shape}")
+    m, D = r.shape
+    idx = np.full((m, k), -1, dtype=np.int32)
+    out = np.zeros((m, k), dtype=np.float32)
+    kk = min(k, D)
+    with np.errstate(all="ignore"):
+        e = r * r
+    key = np.where(np.isnan(e), np.float32(np.inf), e)
+    for i in range(m):
+        order = np.argsort(-key[i], kind="stable")[:kk]
+        idx[i, :kk] = order
+        out[i, :kk] = r[i, order]
+    return idx, out
+
+
+def explain_rows_numpy(detector: Detector, rows: np.ndarray, top_k: int, which=None, dense: bool = False,
+                       engine=None) -> Explanation:
+    """The explanation rule, step by step, on the host (the oracle of
+    ``TorchEngine.explain_rows``): standardise the chosen raw rows, run the
+    fp32 ``functional_forward``, ``resid = y - x``, take ``sse`` (and, for
+    ``hybrid`` + ``cen``, the latents) from the engine's ``forward_rows`` on
+    the same rows, rank by ``select_top_k``.  ``engine``: default a
+    ``TorchEngine`` on the CPU."""
+    from ..engine.base import pad_features
+    from ..models.reference import functional_forward, unflatten
+
+    det = detector
+    k = check_top_k(top_k)
+    if engine is None:
+        from ..engine.torch_engine import TorchEngine
+
+        engine = TorchEngine(det.dims, torch.device("cpu"))
+    if engine.dims != det.dims:
+        raise ValueError(f"the engine's dimensions {engine.dims} are not the detector's {det.dims}")
+    rows = np.asarray(rows)
+    D, Z = det.dims.d_in, det.dims.latent
+    if rows.ndim != 2 or rows.shape[1] != D:
+        raise ValueError(f"rows must be [n, {D}], got {rows.shape}")
+    w = check_which(which, rows.shape[0])
+    m = w.shape[0]
+    cen = det.model_type == "hybrid" and det.latent_scorer == "cen"
+    if m == 0:
+        return Explanation(rows=w, idx=np.zeros((0, k), np.int32), resid=np.zeros((0, k), np.float32),
+                           sse=np.zeros(0, np.float32), resid_full=np.zeros((0, D), np.float32) if dense else None,
+                           latent_terms=np.zeros((0, Z), np.float64) if cen else None)
+    x = det.standardise(rows[w])
+    xp = torch.from_numpy(pad_features(x))
+    with torch.no_grad():
+        xt = xp[:, :D]
+        _, y = functional_forward(unflatten(torch.from_numpy(det.params), det.dims), xt)
+        resid = (y - xt).numpy().astype(np.float32)
+    params = det.padded_params().unsqueeze(0).to(engine.device)
+    sse, lat = engine.forward_rows(params, [(0, xp.to(engine.device))], want_sse=True, want_latent=cen)
+    sse = engine.fetch([sse[0]])[0].astype(np.float32)
+    terms = None
+    if cen:
+        terms = cen_terms_stored(engine.fetch([lat[0]])[0].astype(np.float32), det.latent_mean, det.latent_scale)
+    idx, top = select_top_k(resid, k)
+    return Explanation(rows=w, idx=idx, resid=top, sse=sse, resid_full=resid if dense else None, latent_terms=terms)
+
+
+def expected_raw(detector: Detector, x_std: np.ndarray, resid: np.ndarray, idx: Optional[np.ndarray] = None):
+    """What the model expected, in raw units (float64): the reconstruction
+    ``y = (double)x_std + (double)resid`` put through the inverse of the
+    feature scaler (``standard``: ``y * scale_ + mean_``; ``minmax``: ``(y -
+    min_) / scale_``).  ``x_std`` and ``resid`` are whole rows ``[m, D]``, or,
+    with ``idx`` (``[m, K]`` feature indices; -1: NaN), their entries at those
+    features."""
+    det = detector
+    y = np.asarray(x_std).astype(np.float64) + np.asarray(resid).astype(np.float64)
+    sc = det.scaler
+    a, b = (sc["scale_"], sc["mean_"]) if det.scaler_kind == "standard" else (sc["scale_"], sc["min_"])
+    if idx is None:
+        if y.ndim != 2 or y.shape[1] != det.dims.d_in:
+            raise ValueError(f"x_std and resid must be [m, {det.dims.d_in}], got {y.shape}")
+        sa, sb = a, b
+    else:
+        idx = np.asarray(idx)
+        if idx.shape != y.shape:
+            raise ValueError(f"idx {idx.shape} must match x_std and resid {y.shape}")
+        safe = np.where(idx >= 0, idx, 0)
+        sa, sb = a[safe], b[safe]
+    with np.errstate(all="ignore"):
+        out = y * sa + sb if det.scaler_kind == "standard" else (y - sb) / sa
+    if idx is not None:
+        out = np.where(idx >= 0, out, np.nan)
+    return out

@@ -1,13 +1,21 @@
 """Score raw traffic with an exported detector (README "Deploying a detector").
 
     python -m fedmse_decentralized_amd.detect --detector PATH/detector.npz \\
-        --input traffic.csv [--output alarms.npz] [--backend auto|hip|torch]
+        --input traffic.csv [--output alarms.npz] [--backend auto|hip|torch] [--explain K]
 
 ``--input`` is one headerless CSV of raw feature rows (one column per model
 input) or a directory of them, read in sorted file-name order by the
 package's reader.  ``--output`` receives ``scores`` (float64, cleaned),
 ``flags`` (uint8, 1 = alarm), ``alarms`` and ``threshold``.  One line with the
 row count, the alarm count and the scoring rate goes to stdout.
+
+``--explain K`` (README "Explaining an alarm") also ranks, for every flagged
+row, the K features the model reconstructed worst and adds to ``--output``:
+``explain_rows`` (the flagged rows' indices), ``explain_idx`` (feature indices,
+worst first; -1 unused), ``explain_resid`` (reconstruction minus observation in
+standardised units), ``explain_share`` (the feature's part of the row's squared
+error), ``explain_observed`` and ``explain_expected`` (the raw value and what
+the model expected, in raw units).
 """
 from __future__ import annotations
 
@@ -20,7 +28,7 @@ import numpy as np
 import torch
 
 from .data.csv import load_data
-from .deploy.detector import Detector
+from .deploy.detector import EXPLAIN_MAX_K, Detector, expected_raw
 from .engine import make_engine
 from .ops import _host
 
@@ -39,7 +47,11 @@ def main(argv=None) -> int:
     ap.add_argument("--input", required=True, help="headerless CSV of raw rows, or a directory of them")
     ap.add_argument("--output", default=None, help="write scores and flags to this .npz")
     ap.add_argument("--backend", default="auto", choices=("auto", "hip", "torch"))
+    ap.add_argument("--explain", type=int, default=None, metavar="K",
+                    help=f"rank the K (1..{EXPLAIN_MAX_K}) worst-reconstructed features of every flagged row")
     ns = ap.parse_args(argv)
+    if ns.explain is not None and not 1 <= ns.explain <= EXPLAIN_MAX_K:
+        ap.error(f"--explain takes 1..{EXPLAIN_MAX_K}")
     det = Detector.load(ns.detector)
     rows = read_rows(ns.input)
     if rows.ndim != 2 or rows.shape[1] != det.dims.d_in:
@@ -50,15 +62,35 @@ def main(argv=None) -> int:
     t0 = time.perf_counter()
     scores, flags, alarms = eng.score_rows([det], [rows])[0]
     dt = time.perf_counter() - t0
+    extra, tail = {}, ""
+    if ns.explain is not None:
+        extra = explain_flagged(eng, det, rows, flags, ns.explain)
+        tail = f" explained {extra['explain_rows'].shape[0]} top_k {ns.explain}"
     if ns.output:
         with open(ns.output, "wb") as f:
             np.savez(f, scores=scores, flags=flags, alarms=np.array(alarms, dtype=np.int64),
-                     threshold=np.array(det.threshold, dtype=np.float64))
+                     threshold=np.array(det.threshold, dtype=np.float64), **extra)
     n = int(scores.shape[0])
     rate = n / dt if dt > 0 else float("inf")
     print(f"detect: rows {n} alarms {alarms} threshold {det.threshold:.9g} backend {eng.name} "
-          f"rows_per_s {rate:.1f}")
+          f"rows_per_s {rate:.1f}{tail}")
     return 0
+
+
+def explain_flagged(eng, det: Detector, rows: np.ndarray, flags: np.ndarray, top_k: int) -> dict:
+    """The ``explain_*`` arrays of ``--output`` for the flagged rows."""
+    which = np.flatnonzero(flags).astype(np.int64)
+    ex = eng.explain_rows([det], [rows], top_k=top_k, which=[which])[0]
+    used = ex.idx >= 0
+    col = np.where(used, ex.idx, 0)
+    picked = rows[which]
+    with np.errstate(all="ignore"):
+        e = (ex.resid * ex.resid).astype(np.float64)   # fp32 product, as the ranking key
+        share = np.where(used, e / ex.sse.astype(np.float64)[:, None], 0.0)
+    observed = np.where(used, np.take_along_axis(picked, col, axis=1), np.nan)
+    x_std = np.take_along_axis(det.standardise(picked), col, axis=1)
+    return {"explain_rows": ex.rows, "explain_idx": ex.idx, "explain_resid": ex.resid, "explain_share": share,
+            "explain_observed": observed, "explain_expected": expected_raw(det, x_std, ex.resid, ex.idx)}
 
 
 if __name__ == "__main__":

@@ -285,6 +285,24 @@ class Engine:
         an autoencoder).  The detectors' dimensions need not be the engine's."""
         raise NotImplementedError
 
+    def explain_rows(self, detectors: Sequence, rows: Sequence, top_k: int = 5, which: Optional[Sequence] = None,
+                     dense: bool = False) -> List:
+        """Which features a deployed detector could not reconstruct (README
+        "Explaining an alarm").  ``rows[i]``: the raw feature rows ``[n_i, D]``
+        for ``detectors[i]`` as in ``score_rows``; ``which[i]``: the indices of
+        the rows to explain (any order, repeats allowed; None, or ``which``
+        None: every row).  Returns per detector a ``deploy.detector.Explanation``
+        of numpy arrays: ``rows`` int64 [m]; ``idx`` int32 [m, top_k], the
+        features by falling squared residual (NaN first, equal ones by rising
+        index, -1 past ``min(top_k, D)``); ``resid`` float32 [m, top_k], their
+        residuals ``y - x`` in standardised units (0 where idx is -1); ``sse``
+        float32 [m] with ``forward_rows``' bits; ``resid_full`` float32 [m, D]
+        with ``dense``, else None; ``latent_terms`` float64 [m, Z] for
+        ``hybrid`` + ``cen`` (the score is the root of their sum from column
+        0), else None.  ``top_k`` outside 1..16, an index outside ``[0, n_i)``
+        or rows of the wrong shape raise ValueError."""
+        raise NotImplementedError
+
     def standardize_ddof1(self, x: torch.Tensor) -> torch.Tensor:
         """(x - mean) / (std_ddof1 + 1e-8) over the real D columns
         (`src/Trainer/client_trainer.py:220-223`); the padded columns of the

@@ -23,6 +23,8 @@
 * ``score_rows``    -> ``fedmx_score_rows`` (deployed detectors: raw rows -> scores, alarm
                        flags and counts in one launch; ``fedmx_knn_score`` after it for
                        kNN detectors; not in the reference)
+* ``explain_rows``  -> ``fedmx_explain_rows`` (deployed detectors: per-feature residuals of the
+                       chosen raw rows and their top K in one launch; not in the reference)
 * ``weighted_sum``  -> ``fedmx_weighted_sum`` -- src/Trainer/client_trainer.py:107-130
 * ``robust_aggregate`` -> ``fedmx_robust_agg`` (trimmed mean / median; not in the reference)
 * ``krum_aggregate`` -> ``fedmx_krum_agg`` (Krum / Multi-Krum; not in the reference)
@@ -270,6 +272,39 @@ class HipEngine(Engine):
                 la = None
             out[i] = (s, f, a) + ((la,) if want_latents else ())
         return out
+
+    def explain_rows(self, detectors, rows, top_k=5, which=None, dense=False):
+        """One ``explain_rows_kernel`` launch over every detector's chosen rows
+        (``_hip.explain_rows`` checks ``top_k`` and ``which``; an item with
+        nothing to explain gets no workgroup, and nothing at all launches nothing)."""
+        from ..deploy.detector import Explanation
+
+        which = list(which) if which is not None else [None] * len(detectors)
+        if len(detectors) != len(rows) or len(which) != len(detectors):
+            raise ValueError("explain_rows: one block of rows (and one which) per detector")
+        if not detectors:
+            return []
+        xs = []
+        for det, x in zip(detectors, rows):
+            if not torch.is_tensor(x):
+                x = np.ascontiguousarray(x)
+                if x.dtype not in (np.float32, np.float64):
+                    x = x.astype(np.float64)
+                x = torch.from_numpy(x)
+            if x.dim() != 2 or x.shape[1] != det.dims.d_in:
+                raise ValueError(f"rows must be [n, {det.dims.d_in}], got {tuple(x.shape)}")
+            xs.append(x.to(self.device).contiguous())
+        res = _hip.explain_rows([self._score_state(det)[0] for det in detectors], xs, top_k, which=which, dense=dense)
+        for r, x in zip(res, xs):   # (formed while the launch runs)
+            if r["rows"] is None:
+                r["rows"] = np.arange(int(x.shape[0]), dtype=np.int64)
+        self._rt.sync()
+
+        def host(t):
+            return t.cpu().numpy() if t is not None else None
+
+        return [Explanation(rows=r["rows"], idx=host(r["idx"]), resid=host(r["resid"]), sse=host(r["sse"]),
+                            resid_full=host(r["resid_full"]), latent_terms=host(r["latent_terms"])) for r in res]
 
     def standardize_ddof1(self, x):
         return _hip.standardize_ddof1(x.contiguous(), self.dims.d_in)

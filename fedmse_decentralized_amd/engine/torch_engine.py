@@ -300,6 +300,20 @@ class TorchEngine(Engine):
             out.append(score_rows_numpy(det, x, engine=eng, want_latents=want_latents))
         return out
 
+    def explain_rows(self, detectors, rows, top_k=5, which=None, dense=False):
+        from ..deploy.detector import check_top_k, explain_rows_numpy
+
+        check_top_k(top_k)
+        which = list(which) if which is not None else [None] * len(detectors)
+        if len(detectors) != len(rows) or len(which) != len(detectors):
+            raise ValueError("explain_rows: one block of rows (and one which) per detector")
+        out = []
+        for det, x, w in zip(detectors, rows, which):
+            x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+            eng = self if det.dims == self.dims else TorchEngine(det.dims, self.device)
+            out.append(explain_rows_numpy(det, x, top_k, which=w, dense=dense, engine=eng))
+        return out
+
     def standardize_ddof1(self, x):
         D = self.dims.d_in
         xr = x[:, :D]

@@ -96,6 +96,13 @@ SCORE_DTYPE = np.dtype([
 ])
 SCORE_RAW_F64, SCORE_MINMAX, SCORE_KIND_AE, SCORE_KIND_CEN = 1, 2, 4, 8
 SCORE_CHUNK_ROWS = 64    # rows a score_rows workgroup takes per pass: four waves, one 16-row tile each
+# fedmx_explain.hip ExplainDesc
+EXPLAIN_DTYPE = np.dtype([
+    ("params", "<u8"), ("raw", "<u8"), ("sc_a", "<u8"), ("sc_b", "<u8"), ("z_mean", "<u8"), ("z_scale", "<u8"),
+    ("which", "<u8"), ("idx", "<u8"), ("resid", "<u8"), ("sse", "<u8"), ("resid_full", "<u8"), ("latent_terms", "<u8"),
+    ("nrows", "<i4"), ("d_in", "<i4"), ("hidden", "<i4"), ("latent", "<i4"), ("flags", "<i4"), ("top_k", "<i4"),
+])
+from ..deploy.detector import EXPLAIN_MAX_K, check_top_k, check_which  # noqa: E402  (the rule's one definition)
 
 
 class TrainArgs(ctypes.Structure):
@@ -210,6 +217,8 @@ def lib():
                 "fedmx_detect": [vp, i32, vp],
                 "fedmx_score_rows": [vp, i32, vp],
                 "fedmx_score_chunk_rows": [],
+                "fedmx_explain_rows": [vp, i32, vp],
+                "fedmx_explain_max_k": [],
                 "fedmx_score_reduce": [vp, i32, i32, vp],
                 "fedmx_score_reduce_copy": [vp, i32, i32, vp, i32, vp],
                 "fedmx_broadcast_rows": [vp, vp, vp, i32, vp, i32, vp],
@@ -250,6 +259,8 @@ def lib():
             assert L.fedmx_detect_desc_size() == DETECT_DTYPE.itemsize
             assert L.fedmx_score_desc_size() == SCORE_DTYPE.itemsize
             assert L.fedmx_score_chunk_rows() == SCORE_CHUNK_ROWS
+            assert L.fedmx_explain_desc_size() == EXPLAIN_DTYPE.itemsize
+            assert L.fedmx_explain_max_k() == EXPLAIN_MAX_K
             assert L.fedmx_seg_desc_size() == SEG_DTYPE.itemsize
             assert L.fedmx_train_args_size() == ctypes.sizeof(TrainArgs)
             sz = (ctypes.c_int * 4)()
@@ -1019,6 +1030,121 @@ def score_rows(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], want_
         (dptr,) = rt.desc.put(desc)
         _check(lib().fedmx_score_rows(dptr, len(desc), rt.stream), "fedmx_score_rows")
     return list(zip(scores, flags, lats)), alarms
+
+
+def explain_desc(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], which, outs: Sequence[dict], top_k: int,
+                 rows_per_block: Optional[int] = None) -> np.ndarray:
+    """ExplainDesc array (fedmx_explain.hip): item i explains rows
+    ``which[i]`` (int32 [m] on the device, every entry in ``[0, n)``; None:
+    all ``m = n`` rows in order) of the raw rows ``rows[i]`` ([n, d_in], float64
+    or float32, contiguous) with detector ``states[i]`` into ``outs[i]``:
+    ``idx`` int32 [m, top_k], ``resid`` float32 [m, top_k], ``sse`` float32
+    [m], ``resid_full`` float32 [m, d_in] or None, ``latent_terms`` float64
+    [m, latent] or None (CEN states only).  Every item is cut into blocks of
+    ``rows_per_block`` explained rows, one workgroup each."""
+    k = check_top_k(top_k)
+    if not (len(rows) == len(which) == len(outs) == len(states)):
+        raise ValueError("explain_rows: one rows / which / outputs entry per detector")
+    sizes = np.array([int(x.shape[0]) if w is None else int(w.numel()) for x, w in zip(rows, which)], dtype=np.int64)
+    rpb = rows_per_block or score_rows_per_block(int(sizes.sum()))
+    if rpb % SCORE_CHUNK_ROWS:
+        raise ValueError(f"explain_rows: rows per block must be a multiple of {SCORE_CHUNK_ROWS}")
+    parts = []
+    for i, (st, x, w, o) in enumerate(zip(states, rows, which, outs)):
+        m, dims = int(sizes[i]), st.dims
+        if x.dim() != 2 or x.shape[1] != dims.d_in or x.dtype not in (torch.float32, torch.float64) \
+                or not x.is_contiguous() or x.device != st.device:
+            raise ValueError(f"explain_rows: rows must be contiguous float32 / float64 [n, {dims.d_in}] on the "
+                             "detector's device")
+        if dims.d_in > 127:   # column 127 carries the forward's bias input, not a residual (fedmx_explain.hip)
+            raise ValueError(f"explain_rows: d_in {dims.d_in} reaches the padded layout's bias column")
+        if w is not None and (w.dtype != torch.int32 or w.dim() != 1 or not w.is_contiguous()
+                              or w.device != st.device):
+            raise ValueError("explain_rows: which must be a contiguous int32 vector on the detector's device")
+        want = {"idx": (torch.int32, (m, k)), "resid": (torch.float32, (m, k)), "sse": (torch.float32, (m,)),
+                "resid_full": (torch.float32, (m, dims.d_in)), "latent_terms": (torch.float64, (m, dims.latent))}
+        for name, (dt, shape) in want.items():
+            t = o.get(name)
+            if t is None and name in ("resid_full", "latent_terms"):
+                continue
+            if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != st.device:
+                raise ValueError(f"explain_rows: {name} must be contiguous {dt} {list(shape)} on the detector's device")
+        if o.get("latent_terms") is not None and st.zscaler is None:
+            raise ValueError("explain_rows: latent terms need a CEN detector's latent scaler")
+        if m == 0:
+            continue
+        r0 = np.arange(0, m, rpb, dtype=np.int64)
+        d = np.zeros(len(r0), dtype=EXPLAIN_DTYPE)
+        esz = 8 if x.dtype == torch.float64 else 4
+        d["params"] = st.params.data_ptr()
+        if w is None:
+            d["raw"] = x.data_ptr() + esz * dims.d_in * r0
+        else:
+            d["raw"] = x.data_ptr()
+            d["which"] = w.data_ptr() + 4 * r0
+        d["sc_a"] = st.scaler.data_ptr()
+        d["sc_b"] = st.scaler.data_ptr() + 8 * dims.d_in
+        d["idx"] = o["idx"].data_ptr() + 4 * k * r0
+        d["resid"] = o["resid"].data_ptr() + 4 * k * r0
+        d["sse"] = o["sse"].data_ptr() + 4 * r0
+        if o.get("resid_full") is not None:
+            d["resid_full"] = o["resid_full"].data_ptr() + 4 * dims.d_in * r0
+        if o.get("latent_terms") is not None:
+            d["z_mean"] = st.zscaler.data_ptr()
+            d["z_scale"] = st.zscaler.data_ptr() + 8 * dims.latent
+            d["latent_terms"] = o["latent_terms"].data_ptr() + 8 * dims.latent * r0
+        d["nrows"] = np.minimum(rpb, m - r0)
+        d["d_in"], d["hidden"], d["latent"] = dims.d_in, dims.hidden, dims.latent
+        d["flags"] = (SCORE_RAW_F64 if esz == 8 else 0) | (SCORE_MINMAX if st.minmax else 0)
+        d["top_k"] = k
+        parts.append(d)
+    return np.concatenate(parts) if parts else np.zeros(0, dtype=EXPLAIN_DTYPE)
+
+
+def explain_rows(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], top_k: int, which=None,
+                 dense: bool = False, rows_per_block: Optional[int] = None) -> List[dict]:
+    """Explain raw rows with deployed detectors in one ``explain_rows_kernel``
+    launch (README "Explaining an alarm").  ``which[i]``: the indices into
+    ``rows[i]`` to explain (a host integer array, any order, repeats allowed;
+    checked here to lie in ``[0, n)``), or None for every row.  Returns per
+    item a dict of device tensors, valid after the stream is synchronised:
+    ``idx`` int32 [m, top_k], ``resid`` float32 [m, top_k], ``sse`` float32
+    [m], ``resid_full`` float32 [m, d_in] (``dense``, else None),
+    ``latent_terms`` float64 [m, latent] (CEN states, else None), ``rows``
+    (the checked indices, host int64 [m]; None for every row) and ``which`` (the uploaded
+    indices or None; kept alive until then).  An item with nothing to
+    explain gets empty tensors and no workgroup."""
+    dev = states[0].device
+    rt = runtime(dev)
+    k = check_top_k(top_k)
+    which = list(which) if which is not None else [None] * len(states)
+    if len(which) != len(states) or len(rows) != len(states):
+        raise ValueError("explain_rows: one rows / which entry per detector")
+    wdev, outs, picked = [], [], []
+    for st, x, w in zip(states, rows, which):
+        n = int(x.shape[0])
+        picked.append(None if w is None else check_which(w, n))
+        if w is not None:
+            if n > np.iinfo(np.int32).max:
+                raise ValueError("explain_rows: which indexes at most 2^31 - 1 rows")
+            w = torch.from_numpy(picked[-1].astype(np.int32)).to(dev)
+        m = n if w is None else int(picked[-1].shape[0])
+        wdev.append(w)
+        outs.append({
+            "idx": torch.empty(m, k, dtype=torch.int32, device=dev),
+            "resid": torch.empty(m, k, dtype=torch.float32, device=dev),
+            "sse": torch.empty(m, dtype=torch.float32, device=dev),
+            "resid_full": torch.empty(m, st.dims.d_in, dtype=torch.float32, device=dev) if dense else None,
+            "latent_terms": (torch.empty(m, st.dims.latent, dtype=torch.float64, device=dev)
+                             if st.kind == SCORE_KIND_CEN else None),
+        })
+    desc = explain_desc(states, rows, wdev, outs, k, rows_per_block)
+    if len(desc):
+        (dptr,) = rt.desc.put(desc)
+        _check(lib().fedmx_explain_rows(dptr, len(desc), rt.stream), "fedmx_explain_rows")
+    for o, w, p in zip(outs, wdev, picked):
+        o["which"], o["rows"] = w, p
+    return outs
 
 
 def launch_score_rows(desc_dev: torch.Tensor, n: int, device):

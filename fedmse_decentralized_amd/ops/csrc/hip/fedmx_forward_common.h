@@ -131,16 +131,24 @@ __device__ __forceinline__ void stage_params(const float* __restrict__ p, float*
   }
 }
 
+// fwd_rows_block's default residual sink: takes nothing, costs nothing.
+struct FwdNoSink {
+  __device__ __forceinline__ void operator()(int, int, float) const {}
+};
+
 // Waves `wave` (of `nwaves`) stream the block's 16-row tiles (PREFETCH: the
 // next tile's rows load while this one computes — off when every wave takes
 // at most one tile, which saves 32 VGPRs): 4 chained fp32
 // MFMA layers with the activations kept in registers between layers
 // (transposed orientation, see fedmx_common.h).  `sse` (global or LDS, row
-// indexed) receives per-row sums of squared error over d < d_in.
-template <bool CP, bool PREFETCH = true>
+// indexed) receives per-row sums of squared error over d < d_in.  `sink(u, r,
+// df)` is handed every residual y - x the lane forms, column 16u + 4g + r of
+// its row, padding columns and padding rows included (explain_rows_kernel
+// keeps them; the default drops them).
+template <bool CP, bool PREFETCH = true, class Sink = FwdNoSink>
 __device__ __forceinline__ void fwd_rows_block(const FwdDesc& d, const float* sW1, const float* sW2,
                                                const float* sW3, const float* sW4, int wave, int nwaves,
-                                               float* sse) {
+                                               float* sse, Sink sink = Sink()) {
   const int lane = threadIdx.x & 63;
   const int c = lane & 15;  // batch column (B operand / D column) and A-operand row
   const int g = lane >> 4;  // lane group: k sub-index / D row quad
@@ -259,6 +267,7 @@ __device__ __forceinline__ void fwd_rows_block(const FwdDesc& d, const float* sW
         const int dc = 16 * u + 4 * g + r;
         const float df = acc[r] - x[u][r];
         part += (dc < d.d_in) ? df * df : 0.0f;
+        sink(u, r, df);
       }
     }
     part = sum_lane_groups(part);

@@ -28,7 +28,7 @@
 // LDS: 40,192 B of weights + 4 x (8 KB tile + 64 B SSE + 1 KB latents) + 256 B
 // of latent scaler = 76.8 KB, so two workgroups share a CU's 160 KB.
 #include "fedmx_forward_common.h"
-#include <float.h>
+#include "fedmx_score_common.h"
 
 namespace fedmx {
 
@@ -53,33 +53,8 @@ struct ScoreDesc {
 };
 static_assert(sizeof(ScoreDesc) == 112, "ScoreDesc layout is shared with Python");
 
-constexpr int SCORE_RAW_F64 = 1;   // raw rows are float64 (else float32)
-constexpr int SCORE_MINMAX = 2;    // feature scaler is minmax (else standard)
-constexpr int SCORE_KIND_AE = 4;   // score = mean squared reconstruction error
-constexpr int SCORE_KIND_CEN = 8;  // score = scaled latent's distance to the origin
-constexpr int SCORE_THREADS = 256;
-constexpr int SCORE_WAVES = SCORE_THREADS / 64;
-constexpr int SCORE_TILE = 16;     // rows of one wave's tile (the MFMA batch)
-
-__device__ __forceinline__ double score_clean(double v) {
-  // numpy.nan_to_num: nan -> 0, +-inf -> +-DBL_MAX
-  if (v != v) return 0.0;
-  if (v == INFINITY) return DBL_MAX;
-  if (v == -INFINITY) return -DBL_MAX;
-  return v;
-}
-
-// One feature, as IoTDataProcessor.transform(...).astype(float32) computes it.
-template <bool MINMAX>
-__device__ __forceinline__ float score_standardise(double x, double a, double b) {
-#pragma clang fp contract(off)
-  if (MINMAX) {
-    const double m = x * a;   // rounded on its own: X *= scale_; X += min_
-    return (float)(m + b);
-  }
-  const double s = x - a;     // X -= mean_; X /= scale_
-  return (float)(s / b);
-}
+// (flag bits, SCORE_THREADS / SCORE_WAVES / SCORE_TILE, score_clean and
+// score_standardise: fedmx_score_common.h, shared with explain_rows_kernel)
 
 template <bool CP, bool F64, bool MINMAX>
 __device__ __forceinline__ void score_block(const ScoreDesc& d, const float* sW1, const float* sW2, const float* sW3,

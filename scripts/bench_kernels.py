@@ -271,6 +271,58 @@ def score_rows_timings(args) -> dict:
     return out
 
 
+def explain_rows_timings(args) -> dict:
+    """``--explain-rows``: explain_rows_kernel (fedmx_explain.hip) over the
+    ``--score-n`` raw float64 rows of ``--score-rows`` (same generator, same
+    detectors), event-timed with the rows on the device, beside
+    score_rows_kernel on those rows in the same process: every row at K = 5,
+    5 % of the rows through ``which`` (ascending and shuffled), dense mode, and
+    K = 1 / 16 to split the selection from the rest."""
+    from fedmse_decentralized_amd.data.scaler import StandardScaler
+    from fedmse_decentralized_amd.deploy.detector import Detector
+    from fedmse_decentralized_amd.engine.base import pad_features
+
+    dev = torch.device("cuda", 0)
+    dims = DEFAULT_DIMS
+    n = args.score_n
+    raws = generate_federation(SyntheticSpec(kind="nbaiot", n_clients=1, seed=1))
+    clients, _ = prepare_federation(raws, 1234)
+    sc = dict(clients[0].meta["scaler"])
+    kind = sc.pop("kind")
+    pool = np.concatenate([raws[0].normal, raws[0].abnormal, raws[0].test_normal], 0)
+    rows = pool[np.random.default_rng(3).integers(0, pool.shape[0], size=n)].copy()
+    init, _ = init_client_params(1, 0)
+    eng = HipEngine(dims, dev)
+    ae = Detector(dims=dims, model_type="autoencoder", params=init[0].numpy(), scaler_kind=kind, scaler=sc,
+                  threshold=0.5)
+    params = ae.padded_params().unsqueeze(0).to(dev)
+    train = torch.from_numpy(pad_features(clients[0].train)).to(dev)
+    _, tl = eng.forward_rows(params, [(0, train)], False, True)
+    zs = StandardScaler().fit(eng.fetch([tl[0]])[0])
+    cen = Detector(dims=dims, model_type="hybrid", params=ae.params, scaler_kind=kind, scaler=sc, threshold=1.0,
+                   latent_scorer="cen", latent_mean=zs.mean_, latent_scale=zs.scale_)
+    rows_dev = torch.from_numpy(rows).to(dev)
+    m5 = max(n // 20, 1)
+    rng = np.random.default_rng(4)
+    sub_sorted = np.sort(rng.choice(n, size=m5, replace=False))
+    sub_shuffled = rng.permutation(sub_sorted)
+    out = {"explain_rows_n": n, "explain_rows_subset": m5, "explain_rows_per_block": _hip.score_rows_per_block(n),
+           "explain_rows_subset_per_block": _hip.score_rows_per_block(m5), "explain_rows_input": "float64"}
+    for name, det in (("ae", ae), ("cen", cen)):
+        state, _ = eng._score_state(det)
+        score_us = timeit(lambda: _hip.score_rows([state], [rows_dev]), reps=args.reps)[0]
+        out[f"score_rows_{name}_us"] = score_us
+        cases = {"all_k5": dict(top_k=5), "all_k1": dict(top_k=1), "all_k16": dict(top_k=16),
+                 "all_k5_dense": dict(top_k=5, dense=True),
+                 "subset_sorted_k5": dict(top_k=5, which=[sub_sorted]),
+                 "subset_shuffled_k5": dict(top_k=5, which=[sub_shuffled])}
+        for case, kw in cases.items():
+            us = timeit(lambda: _hip.explain_rows([state], [rows_dev], **kw), reps=args.reps)[0]
+            out[f"explain_rows_{name}_{case}_us"] = us
+            out[f"explain_rows_{name}_{case}_vs_score_rows"] = us / score_us
+    return out
+
+
 def auc_large_timings(args) -> dict:
     """``--auc-large``: the multi-workgroup AUC path (fedmx_auc_large.hip)
     beside the host fallback it replaces, on the same tensors.  Per shape:
@@ -339,6 +391,9 @@ def main():
     p.add_argument("--score-rows", action="store_true", help="only the deployed-detector scoring timings "
                    "(score_rows_kernel over --score-n raw rows, AE and CEN, beside the chain composed from "
                    "transform + pad + copy + forward_rows + cen_scores)")
+    p.add_argument("--explain-rows", action="store_true", help="only the alarm-explanation timings "
+                   "(explain_rows_kernel over --score-n raw rows: all rows at K = 5, 5 %% through which, dense "
+                   "mode, beside score_rows_kernel on the same rows)")
     p.add_argument("--score-n", type=int, default=1_000_000)
     p.add_argument("--latent-scorer", action="store_true", help="only the latent-scorer timings (knn_score_kernel "
                    "beside cen_score_kernel, the evaluation chain and ms / round under either scorer)")
@@ -352,8 +407,9 @@ def main():
     p.add_argument("--reps", type=int, default=20)
     p.add_argument("--train-only", action="store_true", help="only the training-kernel timings (A/B of builds)")
     args = p.parse_args()
-    if args.score_rows or args.auc_large:
-        out = (score_rows_timings if args.score_rows else auc_large_timings)(args)
+    if args.score_rows or args.auc_large or args.explain_rows:
+        out = (score_rows_timings if args.score_rows else explain_rows_timings if args.explain_rows
+               else auc_large_timings)(args)
         print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
         return
     dev = torch.device("cuda", 0)
