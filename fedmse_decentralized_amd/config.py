@@ -107,6 +107,12 @@ class ExperimentConfig:
     # detector (deploy/detector.py: model, feature scaler, latent scorer state,
     # threshold at detect_quantile) as detector.npz beside its model.cpt
     export_detectors: bool = False
+    # with export_detectors: also record in each bundle what "normal" looked
+    # like (README "Monitoring a deployed detector"): the band of the
+    # standardised train features and monitor_bins - 1 edges, order statistics
+    # of the validation scores, with the scores' own bin counts (2..16 bins)
+    export_baseline: bool = False
+    monitor_bins: int = 10
     # --- protocol variants ---------------------------------------------------
     # "first_voter": the reference's decentralised election (first selected
     #   voter that finds an eligible candidate decides, client_trainer.py:249-285);
@@ -194,6 +200,11 @@ class ExperimentConfig:
             raise ValueError(f"latent_scorer must be one of {' | '.join(LATENT_SCORERS)}, got {self.latent_scorer!r}")
         if isinstance(self.knn_k, bool) or not isinstance(self.knn_k, int) or not 1 <= self.knn_k <= KNN_MAX_K:
             raise ValueError(f"knn_k must be an integer in 1..{KNN_MAX_K}, got {self.knn_k!r}")
+        if isinstance(self.monitor_bins, bool) or not isinstance(self.monitor_bins, int) \
+                or not 2 <= self.monitor_bins <= 16:
+            raise ValueError(f"monitor_bins must be an integer in 2..16, got {self.monitor_bins!r}")
+        if self.export_baseline and not self.export_detectors:
+            raise ValueError("export_baseline records the baseline in the exported bundles: it needs export_detectors")
 
     def resolved_init_mode(self) -> str:
         if self.init_mode == "auto":
@@ -241,6 +252,10 @@ _HELP = {
                         "latent scorer state, threshold at --detect-quantile) beside its model.cpt when the "
                         "combination ends; score traffic with python -m fedmse_decentralized_amd.detect "
                         "(default false)",
+    "export_baseline": "with --export-detectors: also record the monitoring baseline in each detector.npz (band of "
+                       "the standardised train features, score edges and counts; python -m "
+                       "fedmse_decentralized_amd.detect --monitor compares live traffic with it) (default false)",
+    "monitor_bins": "--export-baseline: number of score bins of the baseline, 2..16 (default 10)",
     "knn_k": "latent scorer knn: which nearest train latent's distance is the score, 1..16 (default 5)",
     "update_types": "any of: avg fedprox mse_avg fusion_avg trimmed_mean median krum multi_krum",
     "robust_trim_ratio": "share of the selected models assumed poisoned, in [0, 0.5): trimmed_mean drops that "

@@ -42,6 +42,58 @@ LATENT_SCORERS = ("cen", "knn")
 # the scaler vectors each kind stores, in the order the kernel reads them
 SCALER_FIELDS = {"standard": ("mean_", "scale_"), "minmax": ("scale_", "min_")}
 KNN_MAX_K = 16
+MONITOR_MAX_EDGES = 15   # score edges a baseline holds at most (monitor_bins - 1)
+BASELINE_FIELDS = ("feat_lo", "feat_hi", "score_edges", "score_base")
+
+
+@dataclass
+class Baseline:
+    """What "normal" looked like when the detector was exported (README
+    "Monitoring a deployed detector")."""
+    feat_lo: np.ndarray       # float32 [D]: smallest finite standardised train value per feature (+inf: none)
+    feat_hi: np.ndarray       # float32 [D]: largest (-inf: none)
+    score_edges: np.ndarray   # float64 [B], 0 <= B <= 15, non-decreasing: order statistics of the calibration scores
+    score_base: np.ndarray    # int64 [B + 1]: the calibration scores' own bin counts
+
+    def validate(self, d_in: int) -> None:
+        self.feat_lo = _arr(self.feat_lo, np.float32, (d_in,), "baseline feat_lo")
+        self.feat_hi = _arr(self.feat_hi, np.float32, (d_in,), "baseline feat_hi")
+        e = np.asarray(self.score_edges)
+        if e.ndim != 1 or e.shape[0] > MONITOR_MAX_EDGES:
+            raise ValueError(f"baseline score_edges must be a vector of at most {MONITOR_MAX_EDGES} values, "
+                             f"got shape {e.shape}")
+        self.score_edges = _arr(e, np.float64, e.shape, "baseline score_edges")
+        if np.isnan(self.score_edges).any() or np.any(np.diff(self.score_edges) < 0):
+            raise ValueError("baseline score_edges must be non-decreasing numbers")
+        b = np.asarray(self.score_base)
+        if b.dtype.kind not in "iu" or b.shape != (e.shape[0] + 1,):
+            raise ValueError(f"baseline score_base must be {e.shape[0] + 1} integers, got {b.dtype} {b.shape}")
+        self.score_base = np.ascontiguousarray(b, dtype=np.int64)
+        if np.any(self.score_base < 0):
+            raise ValueError("baseline score_base holds counts: none may be negative")
+
+
+def score_bins(scores: np.ndarray, edges: np.ndarray) -> np.ndarray:
+    """int64 [B + 1] bin counts of cleaned scores: ``bin(s) = #{i : edge_i <
+    s}`` (a score equal to an edge falls in the lower bin)."""
+    b = np.searchsorted(np.asarray(edges, dtype=np.float64), np.asarray(scores, dtype=np.float64), side="left")
+    return np.bincount(b, minlength=len(edges) + 1).astype(np.int64)
+
+
+def make_baseline(train_std: np.ndarray, calib_sorted: np.ndarray, bins: int) -> Baseline:
+    """The baseline of fp32 standardised train rows ``[n, D]`` and the sorted
+    cleaned calibration scores, with ``bins`` score bins (2..16)."""
+    if isinstance(bins, bool) or not 2 <= int(bins) <= MONITOR_MAX_EDGES + 1:
+        raise ValueError(f"monitor_bins must be an integer in 2..{MONITOR_MAX_EDGES + 1}, got {bins!r}")
+    x = np.asarray(train_std, dtype=np.float32)
+    fin = np.isfinite(x)
+    lo = np.where(fin, x, np.float32(np.inf)).min(axis=0, initial=np.float32(np.inf)).astype(np.float32)
+    hi = np.where(fin, x, np.float32(-np.inf)).max(axis=0, initial=np.float32(-np.inf)).astype(np.float32)
+    c = np.asarray(calib_sorted, dtype=np.float64)
+    n_c = c.shape[0]
+    edges = np.array([c[calibration_rank(n_c, (i + 1) / bins)] for i in range(int(bins) - 1)] if n_c else [],
+                     dtype=np.float64)
+    return Baseline(feat_lo=lo, feat_hi=hi, score_edges=edges, score_base=score_bins(c, edges))
 
 
 @dataclass
@@ -60,6 +112,7 @@ class Detector:
     train_latents: Optional[np.ndarray] = None  # knn: float32 [n, Z]
     provenance: Dict[str, str] = field(default_factory=dict)
     version: int = FORMAT_VERSION
+    baseline: Optional[Baseline] = None   # what monitor_rows compares live traffic with
 
     def __post_init__(self):
         self.validate()
@@ -83,6 +136,10 @@ class Detector:
         self.threshold = float(self.threshold)
         self.detect_quantile = float(self.detect_quantile)
         self.provenance = {str(k): str(v) for k, v in dict(self.provenance).items()}
+        if self.baseline is not None:
+            if not isinstance(self.baseline, Baseline):
+                raise ValueError(f"baseline must be a Baseline, got {type(self.baseline).__name__}")
+            self.baseline.validate(d.d_in)
         if self.model_type == "autoencoder":
             if self.latent_scorer is not None or self.latent_mean is not None or self.latent_scale is not None \
                     or self.train_latents is not None or self.knn_k:
@@ -129,6 +186,9 @@ class Detector:
             if self.latent_scorer == "knn":
                 arrays["knn_k"] = np.array(self.knn_k, dtype=np.int64)
                 arrays["train_latents"] = self.train_latents
+        if self.baseline is not None:
+            for k in BASELINE_FIELDS:
+                arrays["baseline_" + k] = getattr(self.baseline, k)
         with open(path, "wb") as f:   # (a file object: numpy appends no suffix)
             np.savez(f, **arrays)
         return path
@@ -177,6 +237,15 @@ class Detector:
             if kw["latent_scorer"] == "knn":
                 kw["knn_k"] = _scalar(need("knn_k"), int, "knn_k")
                 kw["train_latents"] = need("train_latents")
+        have = [k for k in BASELINE_FIELDS if "baseline_" + k in a]
+        if have and len(have) != len(BASELINE_FIELDS):
+            raise ValueError(f"{path}: a baseline holds {BASELINE_FIELDS}, the bundle only {tuple(have)}")
+        if have:
+            kw["baseline"] = Baseline(feat_lo=_exact(a["baseline_feat_lo"], np.float32, "baseline feat_lo"),
+                                      feat_hi=_exact(a["baseline_feat_hi"], np.float32, "baseline feat_hi"),
+                                      score_edges=_exact(a["baseline_score_edges"], np.float64,
+                                                         "baseline score_edges"),
+                                      score_base=_exact(a["baseline_score_base"], np.int64, "baseline score_base"))
         return cls(dims=dims, model_type=model_type, params=_exact(need("params"), np.float32, "params"),
                    scaler_kind=kind,
                    scaler={k: _exact(need("scaler_" + k), np.float64, "scaler " + k) for k in SCALER_FIELDS[kind]},
@@ -206,12 +275,15 @@ class Detector:
 
     # -- export ------------------------------------------------------------------------
     @classmethod
-    def from_federation(cls, fed, client_id: int) -> "Detector":
+    def from_federation(cls, fed, client_id: int, baseline: bool = False) -> "Detector":
         """Client ``client_id``'s detector under its current parameters (the
         ones the evaluation evaluates); the client must be hosted by this
         rank.  The threshold is README "Detection thresholds"' tau: the
         ``calibration_rank(n_valid, detect_quantile)``-th smallest cleaned
-        validation score under these parameters (NaN without validation rows)."""
+        validation score under these parameters (NaN without validation rows).
+        ``baseline``: also record the monitoring baseline (README "Monitoring
+        a deployed detector") from the same train rows and validation scores;
+        no further launch."""
         eng, cfg = fed.engine, fed.cfg
         st, dims = eng.store, fed.dims
         if client_id not in fed.local:
@@ -244,6 +316,9 @@ class Detector:
         prov = {"client": client.name, "client_id": str(client_id), "model_type": fed.model_type,
                 "update_type": fed.update_type, "rounds": str(fed.round_idx), "run": str(fed.run),
                 "experiment": cfg.experiment_name}
+        if baseline:
+            train_std = eng.fetch([st.rows("train", loc)])[0][:, :dims.d_in]
+            kw["baseline"] = make_baseline(train_std, calib, cfg.monitor_bins)
         return cls(dims=dims, model_type=fed.model_type, params=params, scaler_kind=sc["kind"],
                    scaler={k: np.asarray(sc[k], dtype=np.float64) for k in SCALER_FIELDS[sc["kind"]]},
                    threshold=tau, detect_quantile=float(cfg.detect_quantile), provenance=prov, **kw)
@@ -481,3 +556,139 @@ def expected_raw(detector: Detector, x_std: np.ndarray, resid: np.ndarray, idx: 
     if idx is not None:
         out = np.where(idx >= 0, out, np.nan)
     return out
+
+
+# ---------------------------------------------------------------------------
+# monitoring a deployed detector (README "Monitoring a deployed detector")
+MONITOR_CHUNK_ROWS = 64   # block_rows is a multiple of it: four waves, one 16-row tile each
+MONITOR_TILE = 16
+MONITOR_WAVES = 4
+
+
+@dataclass
+class DriftReport:
+    """What ``Engine.monitor_rows`` returns per detector (numpy).  The first
+    block is what the rule fixes to the bit; the second is derived from it on
+    the host in float64 (``drift_report``)."""
+    n: int
+    block_rows: int
+    cnt: np.ndarray                     # int64 [D]: finite standardised values
+    bad: np.ndarray                     # int64 [D]: NaN / +-inf ones
+    out: np.ndarray                     # int64 [D]: finite ones outside the baseline's band
+    sum: np.ndarray                     # float64 [D]
+    sq: np.ndarray                      # float64 [D]
+    mn: np.ndarray                      # float32 [D]
+    mx: np.ndarray                      # float32 [D]
+    alarms: int
+    hist: Optional[np.ndarray]          # int64 [B + 1], None without a baseline
+    mean: np.ndarray                    # sum / cnt
+    var: np.ndarray                     # max(sq / cnt - mean^2, 0)
+    out_share: np.ndarray               # out / max(cnt, 1)
+    bad_share: np.ndarray               # bad / max(n, 1)
+    alarm_rate: float                   # alarms / max(n, 1)
+    expected_alarm_rate: float          # 1 - detect_quantile
+    psi: float                          # population stability index of hist against score_base; NaN without
+
+
+def check_block_rows(block_rows) -> int:
+    if isinstance(block_rows, bool) or not isinstance(block_rows, (int, np.integer)) or int(block_rows) < 1 \
+            or int(block_rows) % MONITOR_CHUNK_ROWS:
+        raise ValueError(f"monitor_rows: block_rows must be a positive multiple of {MONITOR_CHUNK_ROWS}, "
+                         f"got {block_rows!r}")
+    return int(block_rows)
+
+
+def drift_report(detector: Detector, n: int, block_rows: int, cnt, bad, out, sum_, sq, mn, mx, alarms,
+                 hist) -> DriftReport:
+    """The report of the rule's results, with the derived float64 values."""
+    cnt, bad, out = (np.ascontiguousarray(v, dtype=np.int64) for v in (cnt, bad, out))
+    sum_, sq = np.ascontiguousarray(sum_, dtype=np.float64), np.ascontiguousarray(sq, dtype=np.float64)
+    mn, mx = np.ascontiguousarray(mn, dtype=np.float32), np.ascontiguousarray(mx, dtype=np.float32)
+    hist = None if hist is None else np.ascontiguousarray(hist, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        c = cnt.astype(np.float64)
+        mean = sum_ / c
+        var = np.maximum(sq / c - mean * mean, 0.0)
+        out_share = out / np.maximum(c, 1.0)
+        bad_share = bad / float(max(n, 1))
+    psi = float("nan")
+    base = detector.baseline
+    if base is not None and hist is not None and base.score_edges.shape[0] > 0:
+        k = hist.shape[0]
+        p = (hist + 0.5) / (float(n) + 0.5 * k)
+        q = (base.score_base + 0.5) / (float(base.score_base.sum()) + 0.5 * k)
+        psi = float(np.sum((p - q) * np.log(p / q)))
+    return DriftReport(n=int(n), block_rows=int(block_rows), cnt=cnt, bad=bad, out=out, sum=sum_, sq=sq, mn=mn, mx=mx,
+                       alarms=int(alarms), hist=hist, mean=mean, var=var, out_share=out_share, bad_share=bad_share,
+                       alarm_rate=int(alarms) / max(int(n), 1), expected_alarm_rate=1.0 - detector.detect_quantile,
+                       psi=psi)
+
+
+def monitor_feature_stats(x_std: np.ndarray, block_rows: int, lo: Optional[np.ndarray], hi: Optional[np.ndarray]):
+    """The per-feature part of the monitoring rule on fp32 standardised rows
+    ``[n, D]``: ``(cnt, bad, out, sum, sq, mn, mx)``.  Every stream (block b,
+    wave w: the block's 16-row tiles w, w + 4, ... in rising order) is
+    accumulated row by row (all streams side by side, one row of each per
+    step), then the streams fold in wave order, the blocks in block order."""
+    R = check_block_rows(block_rows)
+    x = np.asarray(x_std, dtype=np.float32)
+    n, D = x.shape
+    lo = np.full(D, -np.inf, np.float32) if lo is None else np.asarray(lo, dtype=np.float32)
+    hi = np.full(D, np.inf, np.float32) if hi is None else np.asarray(hi, dtype=np.float32)
+    nb = -(-n // R)
+    W = MONITOR_WAVES
+    shape = (nb, W, D)
+    cnt, bad, out = (np.zeros(shape, np.int64) for _ in range(3))
+    s, q = np.zeros(shape, np.float64), np.zeros(shape, np.float64)
+    mn, mx = np.full(shape, np.inf, np.float32), np.full(shape, -np.inf, np.float32)
+    b0 = (np.arange(nb, dtype=np.int64) * R)[:, None]
+    end = np.minimum(n, b0 + R)
+    w = np.arange(W, dtype=np.int64)[None, :]
+    with np.errstate(all="ignore"):
+        for p in range(R // W if nb else 0):   # position in the stream
+            row = b0 + (W * (p // MONITOR_TILE) + w) * MONITOR_TILE + p % MONITOR_TILE   # [nb, W]
+            live = row < end
+            if not live.any():
+                break
+            t = x[np.where(live, row, 0)]                       # [nb, W, D]
+            fin = np.isfinite(t) & live[:, :, None]
+            t64 = t.astype(np.float64)
+            bad += live[:, :, None] & ~fin
+            cnt += fin
+            s = np.where(fin, s + t64, s)
+            q = np.where(fin, q + t64 * t64, q)
+            mn = np.where(fin & (t < mn), t, mn)
+            mx = np.where(fin & (t > mx), t, mx)
+            out += fin & ((t < lo) | (t > hi))
+        # streams -> block: ((p0 + p1) + p2) + p3
+        S, Q, MN, MX = s[:, 0], q[:, 0], mn[:, 0], mx[:, 0]
+        for k in range(1, W):
+            S, Q = S + s[:, k], Q + q[:, k]
+            MN = np.where(mn[:, k] < MN, mn[:, k], MN)
+            MX = np.where(mx[:, k] > MX, mx[:, k], MX)
+        # blocks -> total, in block order from +0.0
+        T, TQ = np.zeros(D, np.float64), np.zeros(D, np.float64)
+        tmn, tmx = np.full(D, np.inf, np.float32), np.full(D, -np.inf, np.float32)
+        for b in range(nb):
+            T, TQ = T + S[b], TQ + Q[b]
+            tmn = np.where(MN[b] < tmn, MN[b], tmn)
+            tmx = np.where(MX[b] > tmx, MX[b], tmx)
+    return cnt.sum(axis=(0, 1)), bad.sum(axis=(0, 1)), out.sum(axis=(0, 1)), T, TQ, tmn, tmx
+
+
+def monitor_rows_numpy(detector: Detector, rows: np.ndarray, block_rows: int, engine=None) -> DriftReport:
+    """The monitoring rule, step by step, on the host (the oracle of
+    ``monitor_rows_kernel`` and what ``TorchEngine.monitor_rows`` runs):
+    ``monitor_feature_stats`` on the standardised rows, ``score_rows_numpy``
+    for the cleaned scores and the alarm count, ``score_bins`` for the
+    histogram.  ``engine``: as in ``score_rows_numpy``."""
+    det = detector
+    R = check_block_rows(block_rows)
+    rows = np.asarray(rows)
+    x = det.standardise(rows)
+    base = det.baseline
+    stats = monitor_feature_stats(x, R, base.feat_lo if base is not None else None,
+                                  base.feat_hi if base is not None else None)
+    scores, _, alarms = score_rows_numpy(det, rows, engine=engine)
+    hist = score_bins(scores, base.score_edges) if base is not None else None
+    return drift_report(det, x.shape[0], R, *stats, alarms, hist)

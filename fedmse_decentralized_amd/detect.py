@@ -2,6 +2,7 @@
 
     python -m fedmse_decentralized_amd.detect --detector PATH/detector.npz \\
         --input traffic.csv [--output alarms.npz] [--backend auto|hip|torch] [--explain K]
+        [--monitor [--monitor-top N]]
 
 ``--input`` is one headerless CSV of raw feature rows (one column per model
 input) or a directory of them, read in sorted file-name order by the
@@ -16,10 +17,19 @@ worst first; -1 unused), ``explain_resid`` (reconstruction minus observation in
 standardised units), ``explain_share`` (the feature's part of the row's squared
 error), ``explain_observed`` and ``explain_expected`` (the raw value and what
 the model expected, in raw units).
+
+``--monitor`` (README "Monitoring a deployed detector") also compares the rows
+with the baseline the bundle was exported with (``--export-baseline``): a second
+line ``monitor: alarm_rate ... expected ... psi ... worst features d:out_share
+...`` names the ``--monitor-top`` (default 5) features with the largest share of
+values outside the train band, and ``--output`` gains one ``monitor_*`` array per
+``DriftReport`` field.  A bundle without a baseline is monitored without band and
+histogram (``baseline none``).
 """
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import os
 import sys
 import time
@@ -49,7 +59,13 @@ def main(argv=None) -> int:
     ap.add_argument("--backend", default="auto", choices=("auto", "hip", "torch"))
     ap.add_argument("--explain", type=int, default=None, metavar="K",
                     help=f"rank the K (1..{EXPLAIN_MAX_K}) worst-reconstructed features of every flagged row")
+    ap.add_argument("--monitor", action="store_true",
+                    help="compare the rows with the bundle's baseline: per-feature drift and score histogram")
+    ap.add_argument("--monitor-top", type=int, default=5, metavar="N",
+                    help="features named on the monitor line, by falling share outside the train band (default 5)")
     ns = ap.parse_args(argv)
+    if ns.monitor_top < 0:
+        ap.error("--monitor-top takes a count >= 0")
     if ns.explain is not None and not 1 <= ns.explain <= EXPLAIN_MAX_K:
         ap.error(f"--explain takes 1..{EXPLAIN_MAX_K}")
     det = Detector.load(ns.detector)
@@ -59,13 +75,20 @@ def main(argv=None) -> int:
                          f"takes {det.dims.d_in}")
     device = "cuda" if ns.backend == "hip" or (ns.backend == "auto" and torch.cuda.is_available()) else "cpu"
     eng = make_engine(ns.backend, det.dims, device)
+    # with --monitor two calls read the rows: on a GPU engine they are uploaded once, ahead of both
+    shared = torch.from_numpy(rows).to(eng.device) if ns.monitor and eng.device.type == "cuda" else rows
     t0 = time.perf_counter()
-    scores, flags, alarms = eng.score_rows([det], [rows])[0]
+    scores, flags, alarms = eng.score_rows([det], [shared])[0]
     dt = time.perf_counter() - t0
     extra, tail = {}, ""
     if ns.explain is not None:
         extra = explain_flagged(eng, det, rows, flags, ns.explain)
         tail = f" explained {extra['explain_rows'].shape[0]} top_k {ns.explain}"
+    monitor_line = None
+    if ns.monitor:
+        rep = eng.monitor_rows([det], [shared])[0]
+        extra.update({"monitor_" + k: np.asarray(v) for k, v in dataclasses.asdict(rep).items() if v is not None})
+        monitor_line = monitor_summary(det, rep, ns.monitor_top)
     if ns.output:
         with open(ns.output, "wb") as f:
             np.savez(f, scores=scores, flags=flags, alarms=np.array(alarms, dtype=np.int64),
@@ -74,7 +97,19 @@ def main(argv=None) -> int:
     rate = n / dt if dt > 0 else float("inf")
     print(f"detect: rows {n} alarms {alarms} threshold {det.threshold:.9g} backend {eng.name} "
           f"rows_per_s {rate:.1f}{tail}")
+    if monitor_line is not None:
+        print(monitor_line)
     return 0
+
+
+def monitor_summary(det: Detector, rep, top: int) -> str:
+    """The ``monitor:`` line: the ``top`` features with the largest
+    ``out_share``, equal shares by rising feature index."""
+    order = np.argsort(-rep.out_share, kind="stable")[:max(0, min(int(top), det.dims.d_in))]
+    worst = " ".join(f"{int(d)}:{rep.out_share[d]:.4g}" for d in order)
+    base = "" if det.baseline is not None else " baseline none"
+    return (f"monitor: alarm_rate {rep.alarm_rate:.6g} expected {rep.expected_alarm_rate:.6g} psi {rep.psi:.6g} "
+            f"worst features {worst}{base}")
 
 
 def explain_flagged(eng, det: Detector, rows: np.ndarray, flags: np.ndarray, top_k: int) -> dict:

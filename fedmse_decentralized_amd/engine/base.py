@@ -303,6 +303,22 @@ class Engine:
         or rows of the wrong shape raise ValueError."""
         raise NotImplementedError
 
+    def monitor_rows(self, detectors: Sequence, rows: Sequence, block_rows: Optional[int] = None) -> List:
+        """Is a deployed detector still looking at the traffic it was trained
+        for (README "Monitoring a deployed detector")?  ``rows[i]``: the raw
+        feature rows ``[n_i, D]`` for ``detectors[i]`` as in ``score_rows``;
+        dimensions, types, scalers, scorers and row counts may differ within
+        one call.  Returns per detector a ``deploy.detector.DriftReport``: per
+        feature the counts of finite (``cnt``) and non-finite (``bad``)
+        standardised values and of those outside the baseline's band
+        (``out``), their float64 ``sum`` and sum of squares ``sq`` in the
+        rule's fixed order, fp32 ``mn`` / ``mx``; the alarm count; the score
+        histogram over the baseline's edges (None without a baseline); and the
+        derived mean, variance, shares, alarm rates and PSI.  ``block_rows``
+        (a multiple of 64; None: ``score_rows_per_block`` of all rows) fixes
+        the summation order and is reported back."""
+        raise NotImplementedError
+
     def standardize_ddof1(self, x: torch.Tensor) -> torch.Tensor:
         """(x - mean) / (std_ddof1 + 1e-8) over the real D columns
         (`src/Trainer/client_trainer.py:220-223`); the padded columns of the

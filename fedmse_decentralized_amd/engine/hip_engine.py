@@ -25,6 +25,9 @@
                        kNN detectors; not in the reference)
 * ``explain_rows``  -> ``fedmx_explain_rows`` (deployed detectors: per-feature residuals of the
                        chosen raw rows and their top K in one launch; not in the reference)
+* ``monitor_rows``  -> ``fedmx_monitor_rows`` (deployed detectors: per-feature statistics of the
+                       standardised rows, alarm count and score histogram in one launch plus
+                       the fold of the block partials; not in the reference)
 * ``weighted_sum``  -> ``fedmx_weighted_sum`` -- src/Trainer/client_trainer.py:107-130
 * ``robust_aggregate`` -> ``fedmx_robust_agg`` (trimmed mean / median; not in the reference)
 * ``krum_aggregate`` -> ``fedmx_krum_agg`` (Krum / Multi-Krum; not in the reference)
@@ -223,6 +226,30 @@ class HipEngine(Engine):
         det._hip_state = (state, train)
         return det._hip_state
 
+    def _rows_on_device(self, x, det=None):
+        """Raw rows (numpy or a tensor; float32 / float64, anything else as
+        float64) as a contiguous tensor on the device; with ``det``, checked
+        to be ``[n, det.dims.d_in]``."""
+        if not torch.is_tensor(x):
+            x = np.ascontiguousarray(x)
+            if x.dtype not in (np.float32, np.float64):
+                x = x.astype(np.float64)
+            x = torch.from_numpy(x)
+        if det is not None and (x.dim() != 2 or x.shape[1] != det.dims.d_in):
+            raise ValueError(f"rows must be [n, {det.dims.d_in}], got {tuple(x.shape)}")
+        return x.to(self.device).contiguous()
+
+    def _knn_scores_grouped(self, detectors, train_lats, lats, which):
+        """``knn_score_kernel`` for the items ``which`` (indices into the three
+        lists), one launch per (k, latent size): ``{item: scores on the device}``."""
+        scores = {}
+        for k in sorted({detectors[j].knn_k for j in which}):
+            for z in sorted({detectors[j].dims.latent for j in which if detectors[j].knn_k == k}):
+                js = [j for j in which if detectors[j].knn_k == k and detectors[j].dims.latent == z]
+                views = _hip.knn_scores([train_lats[j] for j in js], [lats[j] for j in js], z, k)
+                scores.update(zip(js, views))
+        return scores
+
     def score_rows(self, detectors, rows, want_latents=False):
         """One ``score_rows_kernel`` launch over every detector's rows; a knn
         detector's rows leave it as latents and take ``knn_score_kernel`` after
@@ -231,14 +258,7 @@ class HipEngine(Engine):
 
         if len(detectors) != len(rows):
             raise ValueError("score_rows: one block of rows per detector")
-        xs = []
-        for x in rows:
-            if not torch.is_tensor(x):
-                x = np.ascontiguousarray(x)
-                if x.dtype not in (np.float32, np.float64):
-                    x = x.astype(np.float64)
-                x = torch.from_numpy(x)
-            xs.append(x.to(self.device).contiguous())
+        xs = [self._rows_on_device(x) for x in rows]
         out: List[Optional[tuple]] = [None] * len(detectors)
         live = [i for i, x in enumerate(xs) if x.shape[0] > 0]
         for i in set(range(len(xs))) - set(live):   # no rows: nothing to launch
@@ -252,13 +272,9 @@ class HipEngine(Engine):
         states = [self._score_state(detectors[i]) for i in live]
         res, alarms = _hip.score_rows([s for s, _ in states], [xs[i] for i in live],
                                       want_latents=want_latents)
-        knn = [j for j, (s, _) in enumerate(states) if s.kind == 0]
-        knn_scores = {}
-        for k in sorted({detectors[live[j]].knn_k for j in knn}):
-            for z in sorted({detectors[live[j]].dims.latent for j in knn if detectors[live[j]].knn_k == k}):
-                js = [j for j in knn if detectors[live[j]].knn_k == k and detectors[live[j]].dims.latent == z]
-                views = _hip.knn_scores([states[j][1] for j in js], [res[j][2] for j in js], z, k)
-                knn_scores.update(zip(js, views))
+        knn_scores = self._knn_scores_grouped([detectors[i] for i in live], [t for _, t in states],
+                                              [r[2] for r in res],
+                                              [j for j, (s, _) in enumerate(states) if s.kind == 0])
         self._rt.sync()
         counts = alarms.cpu().numpy()
         for j, i in enumerate(live):
@@ -284,16 +300,7 @@ class HipEngine(Engine):
             raise ValueError("explain_rows: one block of rows (and one which) per detector")
         if not detectors:
             return []
-        xs = []
-        for det, x in zip(detectors, rows):
-            if not torch.is_tensor(x):
-                x = np.ascontiguousarray(x)
-                if x.dtype not in (np.float32, np.float64):
-                    x = x.astype(np.float64)
-                x = torch.from_numpy(x)
-            if x.dim() != 2 or x.shape[1] != det.dims.d_in:
-                raise ValueError(f"rows must be [n, {det.dims.d_in}], got {tuple(x.shape)}")
-            xs.append(x.to(self.device).contiguous())
+        xs = [self._rows_on_device(x, det) for det, x in zip(detectors, rows)]
         res = _hip.explain_rows([self._score_state(det)[0] for det in detectors], xs, top_k, which=which, dense=dense)
         for r, x in zip(res, xs):   # (formed while the launch runs)
             if r["rows"] is None:
@@ -305,6 +312,68 @@ class HipEngine(Engine):
 
         return [Explanation(rows=r["rows"], idx=host(r["idx"]), resid=host(r["resid"]), sse=host(r["sse"]),
                             resid_full=host(r["resid_full"]), latent_terms=host(r["latent_terms"])) for r in res]
+
+    def monitor_rows(self, detectors, rows, block_rows=None):
+        """One ``monitor_rows_kernel`` launch over every detector's rows and
+        the ``monitor_fold_kernel`` launch behind it; a knn detector's rows
+        leave the first as latents and take ``knn_score_kernel`` after it, the
+        clean, compare and bin of those on the host.  An item without rows
+        gets no workgroup, and a call without rows launches nothing."""
+        from ..deploy.detector import check_block_rows, clean_and_flag, drift_report, score_bins
+
+        if len(detectors) != len(rows):
+            raise ValueError("monitor_rows: one block of rows per detector")
+        if not detectors:
+            return []
+        xs = [self._rows_on_device(x, det) for det, x in zip(detectors, rows)]
+        rpb = check_block_rows(block_rows if block_rows is not None
+                               else _hip.score_rows_per_block(sum(int(x.shape[0]) for x in xs)))
+
+        def initial(det):   # nothing ran: the rule's initial values
+            D, base = det.dims.d_in, det.baseline
+            stats = (np.zeros(D, np.int64), np.zeros(D, np.int64), np.zeros(D, np.int64), np.zeros(D), np.zeros(D),
+                     np.full(D, np.inf, np.float32), np.full(D, -np.inf, np.float32))
+            h = np.zeros(base.score_edges.shape[0] + 1, np.int64) if base is not None else None
+            return drift_report(det, 0, rpb, *stats, 0, h)
+
+        if not any(x.shape[0] > 0 for x in xs):
+            return [initial(det) for det in detectors]
+        states = [self._score_state(det) for det in detectors]
+        for det, (st, _) in zip(detectors, states):
+            # the band and the edges: uploaded when they differ from what the device holds (at most 271 values)
+            base = det.baseline
+            key = None if base is None else (base.feat_lo.tobytes(), base.feat_hi.tobytes(), base.score_edges.tobytes())
+            if key != getattr(st, "baseline_key", None):
+                if base is None:
+                    st.band = st.edges = None
+                    st.nedges = -1
+                else:
+                    st.set_baseline(base.feat_lo, base.feat_hi, base.score_edges)
+                st.baseline_key = key
+        total, alarms, hist, lats, rpb, part = _hip.monitor_rows([s for s, _ in states], xs, rows_per_block=rpb)
+        knn_scores = self._knn_scores_grouped(detectors, [t for _, t in states], lats,
+                                              [i for i, (s, _) in enumerate(states)
+                                               if s.kind == 0 and xs[i].shape[0] > 0])
+        self._rt.sync()
+        tot = total.cpu().numpy().view(_hip.MONITOR_TOTAL_DTYPE)
+        counts, hists = alarms.cpu().numpy(), hist.cpu().numpy()
+        del part
+        out = []
+        for i, det in enumerate(detectors):
+            n, D, base = int(xs[i].shape[0]), det.dims.d_in, det.baseline
+            if n == 0:
+                out.append(initial(det))
+                continue
+            t = tot[i]
+            stats = tuple(t[k][:D].copy() for k in ("cnt", "bad", "out", "sum", "sq", "mn", "mx"))
+            if i in knn_scores:
+                s, _, a = clean_and_flag(knn_scores[i].cpu().numpy(), det.threshold)
+                h = score_bins(s, base.score_edges) if base is not None else None
+            else:
+                a = int(counts[i])
+                h = hists[i, :base.score_edges.shape[0] + 1].copy() if base is not None else None
+            out.append(drift_report(det, n, rpb, *stats, a, h))
+        return out
 
     def standardize_ddof1(self, x):
         return _hip.standardize_ddof1(x.contiguous(), self.dims.d_in)

@@ -314,6 +314,24 @@ class TorchEngine(Engine):
             out.append(explain_rows_numpy(det, x, top_k, which=w, dense=dense, engine=eng))
         return out
 
+    def monitor_rows(self, detectors, rows, block_rows=None):
+        from ..deploy.detector import check_block_rows, monitor_rows_numpy
+        from ..ops._hip import score_rows_per_block
+
+        if len(detectors) != len(rows):
+            raise ValueError("monitor_rows: one block of rows per detector")
+        xs = [x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x) for x in rows]
+        for det, x in zip(detectors, xs):
+            if x.ndim != 2 or x.shape[1] != det.dims.d_in:
+                raise ValueError(f"rows must be [n, {det.dims.d_in}], got {x.shape}")
+        rpb = check_block_rows(block_rows if block_rows is not None
+                               else score_rows_per_block(sum(int(x.shape[0]) for x in xs)))
+        out = []
+        for det, x in zip(detectors, xs):
+            eng = self if det.dims == self.dims else TorchEngine(det.dims, self.device)
+            out.append(monitor_rows_numpy(det, x, rpb, engine=eng))
+        return out
+
     def standardize_ddof1(self, x):
         D = self.dims.d_in
         xr = x[:, :D]

@@ -779,7 +779,8 @@ class Federation:
         paths = []
         for c in self.local:
             os.makedirs(self.save_dirs[c], exist_ok=True)
-            paths.append(Detector.from_federation(self, c).save(os.path.join(self.save_dirs[c], "detector.npz")))
+            det = Detector.from_federation(self, c, baseline=self.cfg.export_baseline)
+            paths.append(det.save(os.path.join(self.save_dirs[c], "detector.npz")))
         log.info(f"Exported {len(paths)} detectors ({self.model_type}, {self.update_type})")
         return paths
 

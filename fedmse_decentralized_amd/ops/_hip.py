@@ -102,7 +102,27 @@ EXPLAIN_DTYPE = np.dtype([
     ("which", "<u8"), ("idx", "<u8"), ("resid", "<u8"), ("sse", "<u8"), ("resid_full", "<u8"), ("latent_terms", "<u8"),
     ("nrows", "<i4"), ("d_in", "<i4"), ("hidden", "<i4"), ("latent", "<i4"), ("flags", "<i4"), ("top_k", "<i4"),
 ])
-from ..deploy.detector import EXPLAIN_MAX_K, check_top_k, check_which  # noqa: E402  (the rule's one definition)
+# fedmx_monitor.hip MonitorDesc / MonitorFoldDesc / MonitorPartial / MonitorTotal
+MONITOR_DTYPE = np.dtype([
+    ("params", "<u8"), ("raw", "<u8"), ("sc_a", "<u8"), ("sc_b", "<u8"), ("z_mean", "<u8"), ("z_scale", "<u8"),
+    ("lo", "<u8"), ("hi", "<u8"), ("edges", "<u8"), ("hist", "<u8"), ("lat", "<u8"), ("alarms", "<u8"),
+    ("part", "<u8"), ("threshold", "<f8"),
+    ("nrows", "<i4"), ("d_in", "<i4"), ("hidden", "<i4"), ("latent", "<i4"), ("flags", "<i4"), ("score_scale", "<f4"),
+    ("nedges", "<i4"), ("pad", "<i4"),
+])
+MONITOR_FOLD_DTYPE = np.dtype([("part", "<u8"), ("total", "<u8"), ("nblocks", "<i4"), ("pad", "<i4")])
+MONITOR_COLS = 128       # padded columns: one partial each
+MONITOR_PARTIAL_DTYPE = np.dtype([
+    ("sum", "<f8", (MONITOR_COLS,)), ("sq", "<f8", (MONITOR_COLS,)), ("mn", "<f4", (MONITOR_COLS,)),
+    ("mx", "<f4", (MONITOR_COLS,)), ("cnt", "<u4", (MONITOR_COLS,)), ("bad", "<u4", (MONITOR_COLS,)),
+    ("out", "<u4", (MONITOR_COLS,)), ("pad", "<u4", (MONITOR_COLS,)),
+])
+MONITOR_TOTAL_DTYPE = np.dtype([
+    ("sum", "<f8", (MONITOR_COLS,)), ("sq", "<f8", (MONITOR_COLS,)), ("cnt", "<i8", (MONITOR_COLS,)),
+    ("bad", "<i8", (MONITOR_COLS,)), ("out", "<i8", (MONITOR_COLS,)), ("mn", "<f4", (MONITOR_COLS,)),
+    ("mx", "<f4", (MONITOR_COLS,)),
+])
+from ..deploy.detector import EXPLAIN_MAX_K, MONITOR_MAX_EDGES, check_top_k, check_which  # noqa: E402  (the rule's one definition)
 
 
 class TrainArgs(ctypes.Structure):
@@ -219,6 +239,9 @@ def lib():
                 "fedmx_score_chunk_rows": [],
                 "fedmx_explain_rows": [vp, i32, vp],
                 "fedmx_explain_max_k": [],
+                "fedmx_monitor_rows": [vp, i32, vp, i32, vp],
+                "fedmx_monitor_fold": [vp, i32, vp],
+                "fedmx_monitor_max_edges": [],
                 "fedmx_score_reduce": [vp, i32, i32, vp],
                 "fedmx_score_reduce_copy": [vp, i32, i32, vp, i32, vp],
                 "fedmx_broadcast_rows": [vp, vp, vp, i32, vp, i32, vp],
@@ -261,6 +284,11 @@ def lib():
             assert L.fedmx_score_chunk_rows() == SCORE_CHUNK_ROWS
             assert L.fedmx_explain_desc_size() == EXPLAIN_DTYPE.itemsize
             assert L.fedmx_explain_max_k() == EXPLAIN_MAX_K
+            assert L.fedmx_monitor_desc_size() == MONITOR_DTYPE.itemsize
+            assert L.fedmx_monitor_fold_desc_size() == MONITOR_FOLD_DTYPE.itemsize
+            assert L.fedmx_monitor_partial_size() == MONITOR_PARTIAL_DTYPE.itemsize
+            assert L.fedmx_monitor_total_size() == MONITOR_TOTAL_DTYPE.itemsize
+            assert L.fedmx_monitor_max_edges() == MONITOR_MAX_EDGES
             assert L.fedmx_seg_desc_size() == SEG_DTYPE.itemsize
             assert L.fedmx_train_args_size() == ctypes.sizeof(TrainArgs)
             sz = (ctypes.c_int * 4)()
@@ -946,6 +974,22 @@ class ScoreState:
             if z_mean.shape != (dims.latent,) or z_scale.shape != (dims.latent,):
                 raise ValueError(f"score_rows: the latent scaler must hold {dims.latent} values per vector")
             self.zscaler = torch.from_numpy(np.stack([z_mean, z_scale])).to(dev)
+        self.band = self.edges = None   # the monitoring baseline (set_baseline)
+        self.nedges = -1
+
+    def set_baseline(self, feat_lo: np.ndarray, feat_hi: np.ndarray, score_edges: np.ndarray) -> None:
+        """Upload a monitoring baseline: the band (float32 [d_in] each) and the
+        score edges (float64, at most MONITOR_MAX_EDGES, non-decreasing)."""
+        lo = np.ascontiguousarray(feat_lo, dtype=np.float32)
+        hi = np.ascontiguousarray(feat_hi, dtype=np.float32)
+        e = np.ascontiguousarray(score_edges, dtype=np.float64)
+        if lo.shape != (self.dims.d_in,) or hi.shape != (self.dims.d_in,):
+            raise ValueError(f"monitor_rows: the band must hold {self.dims.d_in} values per vector")
+        if e.ndim != 1 or e.shape[0] > MONITOR_MAX_EDGES or np.isnan(e).any() or np.any(np.diff(e) < 0):
+            raise ValueError(f"monitor_rows: at most {MONITOR_MAX_EDGES} non-decreasing score edges")
+        self.band = torch.from_numpy(np.stack([lo, hi])).to(self.device)
+        self.edges = torch.from_numpy(np.concatenate([e, np.zeros(1)])).to(self.device)   # (never empty)
+        self.nedges = int(e.shape[0])
 
 
 def score_desc(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], scores, flags, lats, alarms: torch.Tensor,
@@ -1145,6 +1189,116 @@ def explain_rows(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], top
     for o, w, p in zip(outs, wdev, picked):
         o["which"], o["rows"] = w, p
     return outs
+
+
+def monitor_desc(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], lats, alarms: torch.Tensor,
+                 hist: torch.Tensor, part: torch.Tensor, total: torch.Tensor, rows_per_block: Optional[int] = None):
+    """MonitorDesc and MonitorFoldDesc arrays (fedmx_monitor.hip): item i folds
+    the raw rows ``rows[i]`` ([n, d_in], float64 or float32, contiguous) under
+    detector ``states[i]`` into ``total[i]`` (MONITOR_TOTAL_DTYPE, uint8 view),
+    through one block partial each in ``part`` (MONITOR_PARTIAL_DTYPE, one per
+    descriptor in descriptor order); adds its alarm count to ``alarms[i]``
+    (int32) and, for a state with a baseline, its score histogram to
+    ``hist[16 * i:]`` (int64); a latents-only state (kind 0) writes its latents
+    to ``lats[i]`` (float32 [n, latent]) and counts neither.  Every item is cut
+    into blocks of ``rows_per_block`` rows, one workgroup each; an item without
+    rows gets no descriptor of either kind."""
+    n_items = len(states)
+    if not (len(rows) == len(lats) == n_items) or alarms.numel() < n_items or hist.numel() < 16 * n_items:
+        raise ValueError("monitor_rows: one rows / latents / alarm slot / 16 histogram slots per detector")
+    if alarms.dtype != torch.int32 or not alarms.is_contiguous() or hist.dtype != torch.int64 \
+            or not hist.is_contiguous():
+        raise ValueError("monitor_rows: the alarm counters must be contiguous int32, the histograms int64")
+    sizes = np.array([int(x.shape[0]) for x in rows], dtype=np.int64)
+    rpb = rows_per_block or score_rows_per_block(int(sizes.sum()))
+    if rpb % SCORE_CHUNK_ROWS:
+        raise ValueError(f"monitor_rows: rows per block must be a multiple of {SCORE_CHUNK_ROWS}")
+    nblocks = int(sum(-(-int(n) // rpb) for n in sizes))
+    if part.dtype != torch.uint8 or part.numel() < nblocks * MONITOR_PARTIAL_DTYPE.itemsize \
+            or not part.is_contiguous() or total.dtype != torch.uint8 \
+            or total.numel() < n_items * MONITOR_TOTAL_DTYPE.itemsize or not total.is_contiguous():
+        raise ValueError("monitor_rows: the workspace holds one partial per block and one total per detector")
+    parts, folds, b0 = [], [], 0
+    for i, (st, x, la) in enumerate(zip(states, rows, lats)):
+        n, dims = int(sizes[i]), st.dims
+        if x.dim() != 2 or x.shape[1] != dims.d_in or x.dtype not in (torch.float32, torch.float64) \
+                or not x.is_contiguous() or x.device != st.device:
+            raise ValueError(f"monitor_rows: rows must be contiguous float32 / float64 [n, {dims.d_in}] on the "
+                             "detector's device")
+        if (la is not None) != (st.kind == 0):
+            raise ValueError("monitor_rows: a latents-only item needs latents, a scoring item none")
+        if la is not None and (la.dtype != torch.float32 or tuple(la.shape) != (n, dims.latent)
+                               or not la.is_contiguous() or la.device != st.device):
+            raise ValueError(f"monitor_rows: latents must be contiguous float32 [n, {dims.latent}]")
+        if n == 0:
+            continue
+        r0 = np.arange(0, n, rpb, dtype=np.int64)
+        d = np.zeros(len(r0), dtype=MONITOR_DTYPE)
+        esz = 8 if x.dtype == torch.float64 else 4
+        d["params"] = st.params.data_ptr()
+        d["raw"] = x.data_ptr() + esz * dims.d_in * r0
+        d["sc_a"] = st.scaler.data_ptr()
+        d["sc_b"] = st.scaler.data_ptr() + 8 * dims.d_in
+        if st.zscaler is not None:
+            d["z_mean"] = st.zscaler.data_ptr()
+            d["z_scale"] = st.zscaler.data_ptr() + 8 * dims.latent
+        if st.band is not None:
+            d["lo"] = st.band.data_ptr()
+            d["hi"] = st.band.data_ptr() + 4 * dims.d_in
+            d["edges"] = st.edges.data_ptr()
+            d["nedges"] = st.nedges
+            if st.kind != 0:
+                d["hist"] = hist.data_ptr() + 8 * 16 * i
+        if la is not None:
+            d["lat"] = la.data_ptr() + 4 * dims.latent * r0
+        d["alarms"] = alarms.data_ptr() + 4 * i
+        d["part"] = part.data_ptr() + MONITOR_PARTIAL_DTYPE.itemsize * (b0 + np.arange(len(r0), dtype=np.int64))
+        d["threshold"] = st.threshold
+        d["nrows"] = np.minimum(rpb, n - r0)
+        d["d_in"], d["hidden"], d["latent"] = dims.d_in, dims.hidden, dims.latent
+        d["flags"] = (SCORE_RAW_F64 if esz == 8 else 0) | (SCORE_MINMAX if st.minmax else 0) | st.kind
+        d["score_scale"] = np.float32(1.0 / dims.d_in)
+        parts.append(d)
+        f = np.zeros(1, dtype=MONITOR_FOLD_DTYPE)
+        f["part"] = part.data_ptr() + MONITOR_PARTIAL_DTYPE.itemsize * b0
+        f["total"] = total.data_ptr() + MONITOR_TOTAL_DTYPE.itemsize * i
+        f["nblocks"] = len(r0)
+        folds.append(f)
+        b0 += len(r0)
+    if not parts:
+        return np.zeros(0, dtype=MONITOR_DTYPE), np.zeros(0, dtype=MONITOR_FOLD_DTYPE)
+    return np.concatenate(parts), np.concatenate(folds)
+
+
+def monitor_rows(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], rows_per_block: Optional[int] = None):
+    """Monitor raw rows with deployed detectors (README "Monitoring a
+    deployed detector"): one ``monitor_rows_kernel`` launch over all items and
+    one ``monitor_fold_kernel`` launch behind it.  Returns, valid after the
+    stream is synchronised: ``total`` (uint8 device tensor; view it as
+    MONITOR_TOTAL_DTYPE, one record per item; an item without rows keeps
+    zeros), the int32 alarm counters, the int64 histograms ``[items, 16]``, the
+    per-item latents (latents-only states, else None), the rows per block
+    used and the block-partial workspace (keep it until then).  Nothing
+    launches when no item has rows."""
+    dev = states[0].device
+    rt = runtime(dev)
+    n_items = len(states)
+    sizes = [int(x.shape[0]) for x in rows]
+    rpb = rows_per_block or score_rows_per_block(sum(sizes))
+    if rpb % SCORE_CHUNK_ROWS:
+        raise ValueError(f"monitor_rows: rows per block must be a multiple of {SCORE_CHUNK_ROWS}")
+    nblocks = sum(-(-n // rpb) for n in sizes)
+    alarms = torch.zeros(n_items, dtype=torch.int32, device=dev)
+    hist = torch.zeros(n_items, 16, dtype=torch.int64, device=dev)
+    part = torch.empty(max(nblocks, 1) * MONITOR_PARTIAL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    total = torch.zeros(n_items * MONITOR_TOTAL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    lats = [torch.empty(n, st.dims.latent, dtype=torch.float32, device=dev) if st.kind == 0 else None
+            for st, n in zip(states, sizes)]
+    desc, fold = monitor_desc(states, rows, lats, alarms, hist, part, total, rpb)
+    if len(desc):
+        dptr, fptr = rt.desc.put(desc, fold)
+        _check(lib().fedmx_monitor_rows(dptr, len(desc), fptr, len(fold), rt.stream), "fedmx_monitor_rows")
+    return total, alarms, hist, lats, rpb, part
 
 
 def launch_score_rows(desc_dev: torch.Tensor, n: int, device):

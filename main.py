@@ -164,6 +164,8 @@ def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     add_arguments(p)
     ns = p.parse_args(argv)
+    if ns.export_baseline and not ns.export_detectors:
+        p.error("--export-baseline needs --export-detectors")
     cfg = from_args(ns)
     import os
 

@@ -323,6 +323,98 @@ def explain_rows_timings(args) -> dict:
     return out
 
 
+def monitor_rows_timings(args) -> dict:
+    """``--monitor-rows``: monitor_rows_kernel + monitor_fold_kernel
+    (fedmx_monitor.hip) over the ``--score-n`` raw float64 rows of
+    ``--score-rows`` (same generator, same detectors, each with a baseline of
+    its own train rows and 10 score bins), event-timed with the rows on the
+    device, beside score_rows_kernel on those rows in the same process; then
+    host to host: ``HipEngine.monitor_rows`` on host rows (upload, both
+    launches, read-back, report) beside host numpy computing the same report
+    (``TorchEngine.monitor_rows``, the oracle, with the same block size; CEN).
+    The two kernels are also timed apart.  ``--monitor-kernels-only`` stops
+    after the event-timed figures (A/B of builds through ``FEDMX_HIP_LIB``)."""
+    import time
+
+    from fedmse_decentralized_amd.data.scaler import StandardScaler
+    from fedmse_decentralized_amd.deploy.detector import Detector, make_baseline, score_rows_numpy
+    from fedmse_decentralized_amd.engine.base import pad_features
+
+    dev = torch.device("cuda", 0)
+    dims = DEFAULT_DIMS
+    n = args.score_n
+    raws = generate_federation(SyntheticSpec(kind="nbaiot", n_clients=1, seed=1))
+    clients, _ = prepare_federation(raws, 1234)
+    sc = dict(clients[0].meta["scaler"])
+    kind = sc.pop("kind")
+    pool = np.concatenate([raws[0].normal, raws[0].abnormal, raws[0].test_normal], 0)
+    rows = pool[np.random.default_rng(3).integers(0, pool.shape[0], size=n)].copy()
+    init, _ = init_client_params(1, 0)
+    eng = HipEngine(dims, dev)
+    ae = Detector(dims=dims, model_type="autoencoder", params=init[0].numpy(), scaler_kind=kind, scaler=sc,
+                  threshold=0.5, detect_quantile=0.95)
+    params = ae.padded_params().unsqueeze(0).to(dev)
+    train = torch.from_numpy(pad_features(clients[0].train)).to(dev)
+    _, tl = eng.forward_rows(params, [(0, train)], False, True)
+    zs = StandardScaler().fit(eng.fetch([tl[0]])[0])
+    cen = Detector(dims=dims, model_type="hybrid", params=ae.params, scaler_kind=kind, scaler=sc, threshold=1.0,
+                   detect_quantile=0.95, latent_scorer="cen", latent_mean=zs.mean_, latent_scale=zs.scale_)
+    rows_dev = torch.from_numpy(rows).to(dev)
+    rpb = _hip.score_rows_per_block(n)
+    out = {"monitor_rows_n": n, "monitor_rows_per_block": rpb, "monitor_rows_workgroups": -(-n // rpb),
+           "monitor_rows_input": "float64", "monitor_rows_bins": 10}
+    for name, det in (("ae", ae), ("cen", cen)):
+        valid_scores = np.sort(eng.score_rows([det], [raws[0].normal[:2000]])[0][0])
+        det.baseline = make_baseline(clients[0].train[:, :dims.d_in], valid_scores, 10)
+        det.validate()
+        state, _ = eng._score_state(det)
+        state.set_baseline(det.baseline.feat_lo, det.baseline.feat_hi, det.baseline.score_edges)
+        score_us = timeit(lambda: _hip.score_rows([state], [rows_dev]), reps=args.reps)[0]
+        us = timeit(lambda: _hip.monitor_rows([state], [rows_dev]), reps=args.reps)[0]
+        out[f"score_rows_{name}_us"] = score_us
+        out[f"monitor_rows_{name}_us"] = us
+        out[f"monitor_rows_{name}_vs_score_rows"] = us / score_us
+        # the two launches apart, on one descriptor set (no allocation, no zeroing in the timed span)
+        total, alarms, hist, lats, _, part = _hip.monitor_rows([state], [rows_dev])
+        desc, fold = _hip.monitor_desc([state], [rows_dev], lats, alarms, hist, part, total, rpb)
+        rt = _hip.runtime(dev)
+        dptr, fptr = rt.desc.put(desc, fold)
+        L = _hip.lib()
+        out[f"monitor_rows_kernel_{name}_us"] = timeit(
+            lambda: _hip._check(L.fedmx_monitor_rows(dptr, len(desc), fptr, 0, rt.stream), "fedmx_monitor_rows"),
+            reps=args.reps)[0]
+        out[f"monitor_fold_kernel_{name}_us"] = timeit(
+            lambda: _hip._check(L.fedmx_monitor_fold(fptr, len(fold), rt.stream), "fedmx_monitor_fold"),
+            reps=args.reps)[0]
+        out[f"monitor_rows_kernel_{name}_vs_score_rows"] = out[f"monitor_rows_kernel_{name}_us"] / score_us
+        if args.monitor_kernels_only:
+            continue
+        eng.monitor_rows([det], [rows[:4096]])
+        t0 = time.perf_counter()
+        rep = eng.monitor_rows([det], [rows])[0]
+        out[f"monitor_rows_{name}_host_to_host_ms"] = (time.perf_counter() - t0) * 1e3
+        out[f"monitor_rows_{name}_alarm_rate"] = rep.alarm_rate
+        out[f"monitor_rows_{name}_psi"] = rep.psi
+        out[f"monitor_rows_{name}_max_out_share"] = float(rep.out_share.max())
+    if args.monitor_kernels_only:
+        return out
+    # host numpy computing the same report: the oracle, on the same rows with the same block size
+    from fedmse_decentralized_amd.engine.torch_engine import TorchEngine
+
+    host = TorchEngine(dims, torch.device("cpu"))
+    t0 = time.perf_counter()
+    want = host.monitor_rows([cen], [rows], block_rows=rep.block_rows)[0]
+    out["monitor_rows_cen_host_numpy_ms"] = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    cen.standardise(rows)
+    out["monitor_rows_host_transform_ms"] = (time.perf_counter() - t0) * 1e3
+    out["monitor_rows_cen_sums_equal_host"] = bool(want.sum.tobytes() == rep.sum.tobytes()
+                                                   and want.sq.tobytes() == rep.sq.tobytes()
+                                                   and np.array_equal(want.cnt, rep.cnt)
+                                                   and np.array_equal(want.out, rep.out))
+    return out
+
+
 def auc_large_timings(args) -> dict:
     """``--auc-large``: the multi-workgroup AUC path (fedmx_auc_large.hip)
     beside the host fallback it replaces, on the same tensors.  Per shape:
@@ -394,6 +486,11 @@ def main():
     p.add_argument("--explain-rows", action="store_true", help="only the alarm-explanation timings "
                    "(explain_rows_kernel over --score-n raw rows: all rows at K = 5, 5 %% through which, dense "
                    "mode, beside score_rows_kernel on the same rows)")
+    p.add_argument("--monitor-rows", action="store_true", help="only the drift-monitoring timings "
+                   "(monitor_rows_kernel + monitor_fold_kernel over --score-n raw rows, AE and CEN, beside "
+                   "score_rows_kernel on the same rows and host numpy computing the feature statistics)")
+    p.add_argument("--monitor-kernels-only", action="store_true", help="with --monitor-rows: only the event-timed "
+                   "launches (to compare builds of the kernel library)")
     p.add_argument("--score-n", type=int, default=1_000_000)
     p.add_argument("--latent-scorer", action="store_true", help="only the latent-scorer timings (knn_score_kernel "
                    "beside cen_score_kernel, the evaluation chain and ms / round under either scorer)")
@@ -407,9 +504,9 @@ def main():
     p.add_argument("--reps", type=int, default=20)
     p.add_argument("--train-only", action="store_true", help="only the training-kernel timings (A/B of builds)")
     args = p.parse_args()
-    if args.score_rows or args.auc_large or args.explain_rows:
+    if args.score_rows or args.auc_large or args.explain_rows or args.monitor_rows:
         out = (score_rows_timings if args.score_rows else explain_rows_timings if args.explain_rows
-               else auc_large_timings)(args)
+               else monitor_rows_timings if args.monitor_rows else auc_large_timings)(args)
         print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
         return
     dev = torch.device("cuda", 0)
