@@ -35,6 +35,7 @@ from __future__ import annotations
 import ctypes
 import logging
 import os
+from collections import Counter
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -61,6 +62,35 @@ def wait_chunk_cap(world: int, ranks_on_device: int, max_chunks: int) -> int:
     return max(1, min(max_chunks, WAIT_WORKGROUP_BUDGET // (max(1, world) * max(1, ranks_on_device))))
 
 
+def job_chunk_cap(world: int, peer_devices, max_chunks: int) -> int:
+    """The ONE chunk cap of a job: ``wait_chunk_cap`` for the busiest physical
+    device (``peer_devices``: every rank's device identity, the same list on
+    every rank).  The pusher and the receiver of a chunk must cut a call
+    alike -- the push publishes flag c after writing [c * chunk_words, ...)
+    and the wait on flag c reads [c * chunk_words, ...) -- so the cap cannot
+    depend on how many ranks share the asking rank's own device: with 9 ranks
+    on 8 GPUs that gave the two co-located ranks 1024 // (9 * 2) = 56 chunks
+    and the seven others 64.  The budget argument still holds: the busiest
+    device carries max_share x world x cap <= WAIT_WORKGROUP_BUDGET waiting
+    workgroups, and every other device, with fewer ranks under the same cap,
+    fewer than that."""
+    ids = [tuple(i) for i in peer_devices]
+    max_share = max(Counter(ids).values()) if ids else 1
+    return wait_chunk_cap(world, max_share, max_chunks)
+
+
+def chunk_plan(n_words: int, max_chunks: int, chunk_target: int = 1024):
+    """(chunks, chunk_words) of one gather of ``n_words`` 32-bit words: about
+    ``chunk_target`` words per chunk, at most ``max_chunks`` chunks, whole
+    f32x4 per chunk, and no chunk that starts at or past ``n_words``."""
+    n = int(n_words)
+    chunks = max(1, min(int(max_chunks), -(-n // int(chunk_target))))
+    cw = ((-(-n // chunks)) + 3) & ~3
+    # (rounding chunk_words up to 4 can leave the last chunks empty: drop them)
+    chunks = max(1, -(-n // cw)) if cw else 1
+    return chunks, cw
+
+
 class _Channel:
     """One receive area per rank plus the sequence counter of its calls."""
 
@@ -84,10 +114,12 @@ class _Channel:
         # ranks x 8 sources x 64 chunks = 4,096 spinning workgroups could
         # leave the peers' push kernels no CU to run on.  The chunk count is
         # capped so that all co-located ranks' wait grids together stay
-        # within half of that (1,024 workgroups); a rank alone on its GPU keeps
-        # up to IPC_MAX_CHUNKS.  (Round 6 suspected this of round 5's failed
-        # second bring-up; the cap alone did not cure it -- IpcComm._teardown.)
-        self.max_chunks = wait_chunk_cap(W, comm.ranks_per_device(), _hip.IPC_MAX_CHUNKS)
+        # within half of that (1,024 workgroups); a job with one rank per GPU
+        # keeps up to IPC_MAX_CHUNKS.  The cap is the job's, from its busiest
+        # device, so that every rank cuts a call alike (job_chunk_cap).  (Round
+        # 6 suspected this of round 5's failed second bring-up; the cap alone
+        # did not cure it -- IpcComm._teardown.)
+        self.max_chunks = job_chunk_cap(W, comm.device_identities(), _hip.IPC_MAX_CHUNKS)
         nbytes = 4 * (2 * W * self.slot_words + 2 * W * _hip.IPC_MAX_CHUNKS)
         hsz = self.L.fedmx_ipc_handle_size()
         handle = (ctypes.c_uint8 * hsz)()
@@ -156,8 +188,7 @@ class _Channel:
 
     def gather(self, out: torch.Tensor, t: torch.Tensor, stream: int) -> None:
         n = t.numel()
-        chunks = max(1, min(self.max_chunks, -(-n // self.chunk_target)))
-        cw = ((-(-n // chunks)) + 3) & ~3
+        chunks, cw = chunk_plan(n, self.max_chunks, self.chunk_target)
         a = self._args(t.data_ptr(), out.data_ptr(), n, chunks, cw)
         self.H._check(self.L.fedmx_ipc_push(ctypes.byref(a), stream), "fedmx_ipc_push")
         self.H._check(self.L.fedmx_ipc_wait_gather(ctypes.byref(a), stream), "fedmx_ipc_wait_gather")
@@ -219,18 +250,16 @@ class IpcComm(TorchDistComm):
     def base_all_gather_object(self, obj):
         return TorchDistComm.all_gather_object(self, obj)
 
-    def ranks_per_device(self) -> int:
-        """How many ranks of the job run on this rank's physical GPU (the
-        collective self-test's device identities, or asked now); collective
-        when they are not known yet."""
+    def device_identities(self) -> list:
+        """Every rank's (host, physical GPU), the same list on every rank (the
+        collective self-test's, or asked now); collective when not known yet."""
         ids = getattr(self, "peer_devices", None)
         if ids is None:
             from .launch import _device_identity
 
             ids = self.base_all_gather_object(_device_identity(self.device))
             self.peer_devices = ids
-        mine = ids[self.rank]
-        return max(1, sum(1 for i in ids if tuple(i) == tuple(mine)))
+        return ids
 
     def setup_exchange(self, gather_words: int, reduce_words: int) -> bool:
         """Create (or keep, when large enough) the two channels; collective.

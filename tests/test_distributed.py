@@ -278,3 +278,70 @@ def test_ipc_wait_grid_fits_the_device():
         assert c >= 1 and world * c * share <= WAIT_WORKGROUP_BUDGET, (world, share, c)
     assert wait_chunk_cap(8, 8, 64) == 16
     assert wait_chunk_cap(16, 16, 64) == 4
+
+
+def _mapping(shares):
+    """Device identities of a job whose i-th physical GPU hosts shares[i] ranks
+    (interleaved, so that co-located ranks are not neighbours)."""
+    ids = [("host", f"GPU-{d}") for d, n in enumerate(shares) for _ in range(n)]
+    return ids[1::2] + ids[0::2]
+
+
+def test_ipc_chunk_cap_is_one_per_job():
+    """The pusher and the receiver of a chunk must cut a call alike, so the
+    chunk cap is the job's (its busiest device), not the asking rank's: with 9
+    ranks on 8 GPUs (2/1/1/1/1/1/1/1) the per-rank rule gave the two
+    co-located ranks 1024 // (9 * 2) = 56 and the seven others
+    min(64, 1024 // 9) = 64, and a gather of 7 x 9,216 words was cut as
+    56 x 1,152 by one side and 63 x 1,024 by the other."""
+    import types
+    from collections import Counter
+
+    from fedmse_decentralized_amd.parallel.ipc import (WAIT_WORKGROUP_BUDGET, IpcComm, chunk_plan, job_chunk_cap,
+                                                       wait_chunk_cap)
+
+    for shares, cap in (((2, 1, 1, 1, 1, 1, 1, 1), 56), ((8,), 16), ((1,) * 8, 64), ((3, 3, 2, 1), 37)):
+        ids = _mapping(shares)
+        W = len(ids)
+        assert W == sum(shares)
+        # what each rank computes from its own view of the job (the device
+        # identities are one all-gathered list, the same on every rank)
+        caps = []
+        for rank in range(W):
+            comm = types.SimpleNamespace(rank=rank, world_size=W, peer_devices=[list(i) for i in ids])
+            caps.append(job_chunk_cap(W, IpcComm.device_identities(comm), 64))
+        assert len(set(caps)) == 1, (shares, caps)
+        assert caps[0] == wait_chunk_cap(W, max(shares), 64) == cap, (shares, caps[0])
+        # the budget: the busiest device within it, every other device below
+        per_device = Counter(ids)
+        assert max(per_device.values()) == max(shares)
+        for n in per_device.values():
+            assert n * W * caps[0] <= WAIT_WORKGROUP_BUDGET
+    # the old per-rank rule on the 9-rank mapping: 56 against 64, two cuts of one call
+    ids = _mapping((2, 1, 1, 1, 1, 1, 1, 1))
+    old = [wait_chunk_cap(9, sum(1 for i in ids if i == ids[r]), 64) for r in range(9)]
+    assert sorted(old) == [56, 56] + [64] * 7
+    assert chunk_plan(7 * 9216, 56) == (56, 1152) and chunk_plan(7 * 9216, 64) == (63, 1024)
+    assert job_chunk_cap(1, [], 64) == 64
+
+
+def test_ipc_chunk_plan_covers_the_call_without_empty_chunks():
+    """chunk_plan for every length and every cap: within the cap, whole
+    f32x4 per chunk, the call covered, and no chunk that starts at or past
+    n_words (empty chunks are the kernel test's matter, never production's)."""
+    from fedmse_decentralized_amd.parallel.ipc import chunk_plan
+
+    ns = np.arange(4, 70_001, 4, dtype=np.int64)
+    for cap in range(1, 65):
+        plans = np.array([chunk_plan(n, cap) for n in ns.tolist()], dtype=np.int64)
+        chunks, cw = plans[:, 0], plans[:, 1]
+        assert (chunks >= 1).all() and (chunks <= cap).all(), cap
+        assert (cw % 4 == 0).all(), cap
+        assert (chunks * cw >= ns).all(), cap
+        assert ((chunks - 1) * cw < ns).all(), cap     # the last chunk starts below n_words
+    assert chunk_plan(0, 64) == (1, 0)
+    # a small target, where rounding chunk_words up to 4 would leave empty chunks behind
+    for n in range(4, 400, 4):
+        for cap in (1, 3, 64):
+            chunks, cw = chunk_plan(n, cap, chunk_target=4)
+            assert 1 <= chunks <= cap and cw % 4 == 0 and chunks * cw >= n > (chunks - 1) * cw, (n, cap)

@@ -46,7 +46,9 @@ def _exchange_worker(rank, world, port, out):
     P = 9216
     slots = 5
     ok_setup = comm.setup_exchange((slots + 1) * P, 4 * 10 * world)
-    res = dict(active=ok_setup, gather=[], reduce=[])
+    # the chunk cap of both channels: one per job, or pusher and receiver cut a call differently
+    res = dict(active=ok_setup, gather=[], reduce=[],
+               caps=[ch.max_chunks for ch in (comm._gather, comm._reduce)] if ok_setup else None)
     side = torch.cuda.Stream(device=dev)
     send = torch.zeros((slots + 1) * P, device=dev)
     allg = torch.zeros(world * (slots + 1) * P, device=dev)
@@ -82,11 +84,18 @@ def _exchange_worker(rank, world, port, out):
 def test_ipc_exchange_kernels(tmp_path, world):
     mp.start_processes(_exchange_worker, args=(world, _port(), str(tmp_path)), nprocs=world, join=True,
                        start_method="spawn")
+    from fedmse_decentralized_amd.parallel.ipc import wait_chunk_cap
+
+    caps = []
     for r in range(world):
         d = json.load(open(tmp_path / f"x{r}.json"))
         assert d["active"], d
         assert all(d["gather"]) and all(d["reduce"]), d
         assert d["calls"] == 14 and d["status_ok"]
+        caps.append(d["caps"])
+    # every rank of the job reports the same cap (here: all ranks on one card)
+    assert all(c == caps[0] for c in caps), caps
+    assert caps[0] == [wait_chunk_cap(world, world, 64)] * 2, caps
 
 
 def _fed_worker(rank, world, port, out, network_size=6):
