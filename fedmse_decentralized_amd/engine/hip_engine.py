@@ -157,7 +157,11 @@ class HipEngine(Engine):
         return (self.latent_scorer, int(self.knn_k))
 
     def auc(self, scores, labels):
-        out = self.fetch([_hip.auc(list(scores), list(labels))])[0]
+        # the descriptors carry raw pointers: contiguous copies of strided views, made
+        # once, kept until the fetch has completed and reused by the large path
+        scores = [s.detach().contiguous() for s in scores]
+        labels = list(labels)
+        out = self.fetch([_hip.auc(scores, labels)])[0]
         return self._auc_fixup(out, scores, labels)
 
     def _auc_fixup(self, out, scores, labels, f32_scale: float = 1.0):

@@ -740,16 +740,23 @@ def knn_scores(train_lat: Sequence[torch.Tensor], query_lat: Sequence[torch.Tens
 
 
 def auc_desc(scores, labels, out_ptr: int, f32_scale: float = 1.0) -> np.ndarray:
+    """AucDesc array (fedmx_eval.hip): item i's result goes to float64 slot i
+    of ``out_ptr``.  The kernel reads raw pointers, so anything but a
+    contiguous float32 / float64 vector with one contiguous int32 label per
+    score is refused here."""
     n = len(scores)
+    if len(labels) != n:
+        raise ValueError(f"auc: {n} score vectors but {len(labels)} label vectors")
     desc = np.zeros(n, dtype=AUC_DTYPE)
     for i, (s, l) in enumerate(zip(scores, labels)):
-        if l.dtype != torch.int32:
-            raise ValueError("labels must be int32")
+        f64 = _score_vec(s, "scores", "auc")
+        if l.dtype != torch.int32 or l.dim() != 1 or not l.is_contiguous() or l.shape[0] != s.shape[0]:
+            raise ValueError("auc: labels must be contiguous int32, one per score")
         desc[i]["score"] = s.data_ptr()
         desc[i]["label"] = l.data_ptr()
         desc[i]["out"] = out_ptr + 8 * i
         desc[i]["n"] = s.shape[0]
-        desc[i]["score_is_f64"] = 1 if s.dtype == torch.float64 else 0
+        desc[i]["score_is_f64"] = f64
         desc[i]["score_scale"] = f32_scale
     return desc
 
