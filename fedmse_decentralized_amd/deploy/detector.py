@@ -692,3 +692,150 @@ def monitor_rows_numpy(detector: Detector, rows: np.ndarray, block_rows: int, en
     scores, _, alarms = score_rows_numpy(det, rows, engine=engine)
     hist = score_bins(scores, base.score_edges) if base is not None else None
     return drift_report(det, x.shape[0], R, *stats, alarms, hist)
+
+
+# ---------------------------------------------------------------------------
+# grouping alarms into incidents (README "Incidents")
+INCIDENT_MAX_WINDOW = 4096
+INCIDENT_MAX_HOLD = 4096
+INCIDENT_MAX_ROWS = (1 << 31) - 16384   # n stays below it: a row index plus one span and its halo fits 32 bits
+
+
+@dataclass
+class Incidents:
+    """What ``Engine.incidents`` returns per item (numpy): the incidents of one
+    row sequence under the rule of README "Incidents", in row order."""
+    n: int
+    window: int
+    min_alarms: int
+    hold: int
+    start: np.ndarray        # int64 [k]: first hot row of incident k
+    end: np.ndarray          # int64 [k]: last hot row
+    alarms: np.ndarray       # int64 [k]: flagged rows in [max(0, start - window + 1), end]
+    peak_row: np.ndarray     # int64 [k]: the smallest row of [start, end] holding the range's largest score
+    peak_score: np.ndarray   # float64 [k]: scores[peak_row], its bits as stored
+    hot_rows: int
+    count: int
+    rows_covered: int        # sum of end - start + 1
+    longest: int             # largest end - start + 1 (0 without an incident)
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def check_incident_params(window, min_alarms, hold=0):
+    """``(window, min_alarms, hold)`` as ints; ValueError outside ``1 <= window
+    <= 4096``, ``1 <= min_alarms <= window``, ``0 <= hold <= 4096``."""
+    if not _is_int(window) or not 1 <= int(window) <= INCIDENT_MAX_WINDOW:
+        raise ValueError(f"incidents: window must be an integer in 1..{INCIDENT_MAX_WINDOW}, got {window!r}")
+    if not _is_int(min_alarms) or not 1 <= int(min_alarms) <= int(window):
+        raise ValueError(f"incidents: min_alarms must be an integer in 1..window ({int(window)}), got {min_alarms!r}")
+    if not _is_int(hold) or not 0 <= int(hold) <= INCIDENT_MAX_HOLD:
+        raise ValueError(f"incidents: hold must be an integer in 0..{INCIDENT_MAX_HOLD}, got {hold!r}")
+    return int(window), int(min_alarms), int(hold)
+
+
+def check_incident_rows(flags_shape, scores_shape) -> int:
+    """The row count of one ``(flags, scores)`` item; ValueError unless both
+    are vectors of one length below ``INCIDENT_MAX_ROWS``."""
+    fs, ss = tuple(flags_shape), tuple(scores_shape)
+    if len(fs) != 1 or len(ss) != 1:
+        raise ValueError(f"incidents: flags and scores must be vectors, got shapes {fs} and {ss}")
+    if fs != ss:
+        raise ValueError(f"incidents: {fs[0]} flags for {ss[0]} scores")
+    if fs[0] >= INCIDENT_MAX_ROWS:
+        raise ValueError(f"incidents: at most {INCIDENT_MAX_ROWS - 1} rows per item, got {fs[0]}")
+    return int(fs[0])
+
+
+def incident_bound(n: int, hold: int) -> int:
+    """The most incidents ``n`` rows can hold: starts lie at least ``hold + 2`` apart."""
+    return (int(n) + int(hold) + 1) // (int(hold) + 2)
+
+
+def empty_incidents(n: int, window: int, min_alarms: int, hold: int, hot_rows: int = 0) -> Incidents:
+    z = np.zeros(0, np.int64)
+    return Incidents(n=int(n), window=window, min_alarms=min_alarms, hold=hold, start=z, end=z.copy(),
+                     alarms=z.copy(), peak_row=z.copy(), peak_score=np.zeros(0, np.float64), hot_rows=int(hot_rows),
+                     count=0, rows_covered=0, longest=0)
+
+
+def incidents_numpy(flags, scores, window, min_alarms, hold=0) -> Incidents:
+    """The incident rule on the host, with cumulative sums (the oracle of the
+    kernels in fedmx_incident.hip and what ``TorchEngine.incidents`` runs).
+    ``flags``: any non-zero value counts as 1; ``scores`` are cleaned first
+    (NaN -> 0, +-inf -> +-DBL_MAX).  With ``P`` the prefix count of the flags
+    and ``H`` that of the hot rows: ``cnt[i] = P[i + 1] - P[max(0, i - w + 1)]``,
+    ``hot = cnt >= m``, a start is a hot row with ``H[i] == H[max(0, i - h -
+    1)]``, an end one with ``H[min(n, i + h + 2)] == H[i + 1]``; per incident
+    ``alarms = P[end + 1] - P[max(0, start - w + 1)]`` and the peak is the
+    first row of ``[start, end]`` whose score equals the range's maximum
+    (compared by value: -0.0 equals +0.0)."""
+    w, m, h = check_incident_params(window, min_alarms, hold)
+    f = np.asarray(flags)
+    s = np.asarray(scores)
+    n = check_incident_rows(f.shape, s.shape)
+    if n == 0:
+        return empty_incidents(0, w, m, h)
+    s = np.nan_to_num(s.astype(np.float64))
+    idx = np.arange(n, dtype=np.int64)
+    P = np.concatenate([np.zeros(1, np.int64), np.cumsum(f != 0, dtype=np.int64)])
+    hot = P[idx + 1] - P[np.maximum(idx - w + 1, 0)] >= m
+    H = np.concatenate([np.zeros(1, np.int64), np.cumsum(hot, dtype=np.int64)])
+    start = np.flatnonzero(hot & (H[idx] == H[np.maximum(idx - h - 1, 0)])).astype(np.int64)
+    end = np.flatnonzero(hot & (H[np.minimum(idx + h + 2, n)] == H[idx + 1])).astype(np.int64)
+    k = int(start.shape[0])
+    if end.shape[0] != k or k > incident_bound(n, h):
+        raise AssertionError("incidents: starts and ends do not pair up")   # (the rule excludes it)
+    if k == 0:
+        return empty_incidents(n, w, m, h, hot_rows=int(H[n]))
+    alarms = P[end + 1] - P[np.maximum(start - w + 1, 0)]
+    # the range maxima: reduceat over [s0, e0 + 1, s1, e1 + 1, ...] (strictly rising; a sentinel covers e + 1 == n)
+    cuts = np.stack([start, end + 1], axis=1).reshape(-1)
+    top = np.maximum.reduceat(np.concatenate([s, [-np.inf]]), cuts)[0::2]
+    # rows inside an incident, and which: starts at or before the row, ends before it
+    n_start = np.cumsum(np.bincount(start, minlength=n))
+    n_end = np.concatenate([np.zeros(1, np.int64), np.cumsum(np.bincount(end, minlength=n))[:-1]])
+    inside = n_start > n_end
+    cand = np.flatnonzero(inside & (s == top[np.maximum(n_start - 1, 0)]))
+    which, first = np.unique(n_start[cand] - 1, return_index=True)
+    if which.shape[0] != k:
+        raise AssertionError("incidents: an incident without a peak")
+    peak_row = cand[first].astype(np.int64)
+    length = end - start + 1
+    return Incidents(n=n, window=w, min_alarms=m, hold=h, start=start, end=end, alarms=alarms.astype(np.int64),
+                     peak_row=peak_row, peak_score=s[peak_row].copy(), hot_rows=int(H[n]), count=k,
+                     rows_covered=int(length.sum()), longest=int(length.max()))
+
+
+def incident_min_alarms(window, rate, tail) -> int:
+    """The smallest ``m`` in ``1..window`` with ``P[Binomial(window, rate) >=
+    m] <= tail``, in float64 on the host (``window`` if no m reaches ``tail``).
+
+    The model behind it: benign flags are independent draws at ``rate = 1 -
+    detect_quantile``.  Real traffic is correlated in time, so the value is a
+    starting point for tuning ``min_alarms``, not a guarantee on the rate of
+    false incidents."""
+    import math
+
+    if not _is_int(window) or not 1 <= int(window) <= INCIDENT_MAX_WINDOW:
+        raise ValueError(f"incident_min_alarms: window must be an integer in 1..{INCIDENT_MAX_WINDOW}, got {window!r}")
+    w, rate, tail = int(window), float(rate), float(tail)
+    if not 0.0 <= rate <= 1.0:
+        raise ValueError(f"incident_min_alarms: rate must lie in [0, 1], got {rate!r}")
+    if not 0.0 < tail < 1.0:
+        raise ValueError(f"incident_min_alarms: tail must lie in (0, 1), got {tail!r}")
+    if rate == 0.0:
+        return 1
+    if rate == 1.0:
+        return w
+    lr, lq = math.log(rate), math.log1p(-rate)
+    lg = math.lgamma
+    best, sf = w + 1, 0.0
+    for j in range(w, 0, -1):   # the tail grows as j falls: summed from its small end
+        sf += math.exp(lg(w + 1) - lg(j + 1) - lg(w - j + 1) + j * lr + (w - j) * lq)
+        if sf > tail:
+            break
+        best = j
+    return min(best, w)

@@ -3,6 +3,7 @@
     python -m fedmse_decentralized_amd.detect --detector PATH/detector.npz \\
         --input traffic.csv [--output alarms.npz] [--backend auto|hip|torch] [--explain K]
         [--monitor [--monitor-top N]]
+        [--incidents [--incident-window W] [--incident-min M|auto] [--incident-tail P] [--incident-hold H]]
 
 ``--input`` is one headerless CSV of raw feature rows (one column per model
 input) or a directory of them, read in sorted file-name order by the
@@ -25,6 +26,19 @@ line ``monitor: alarm_rate ... expected ... psi ... worst features d:out_share
 values outside the train band, and ``--output`` gains one ``monitor_*`` array per
 ``DriftReport`` field.  A bundle without a baseline is monitored without band and
 histogram (``baseline none``).
+
+``--incidents`` (README "Incidents") also groups the flagged rows into
+incidents: a row is hot when at least ``--incident-min`` of the last
+``--incident-window`` (default 64) rows are flagged, and hot rows with at most
+``--incident-hold`` (default: the window) other rows between them form one
+incident.  ``--incident-min auto`` (the default) takes the smallest count whose
+chance under independent benign flags at rate ``1 - detect_quantile`` is at
+most ``--incident-tail`` (default 1e-6).  A line ``incidents: count K
+rows_covered R longest L hot_rows H window W min M hold H`` follows, and
+``--output`` gains ``incident_start``, ``incident_end``, ``incident_alarms``,
+``incident_peak_row``, ``incident_peak_score`` and ``incident_params`` (window,
+min, hold).  Rows are in time order: a directory's files are concatenated in
+sorted name order and a window runs across file boundaries.
 """
 from __future__ import annotations
 
@@ -38,7 +52,8 @@ import numpy as np
 import torch
 
 from .data.csv import load_data
-from .deploy.detector import EXPLAIN_MAX_K, Detector, expected_raw
+from .deploy.detector import (EXPLAIN_MAX_K, INCIDENT_MAX_HOLD, INCIDENT_MAX_WINDOW, Detector, expected_raw,
+                              incident_min_alarms)
 from .engine import make_engine
 from .ops import _host
 
@@ -63,7 +78,31 @@ def main(argv=None) -> int:
                     help="compare the rows with the bundle's baseline: per-feature drift and score histogram")
     ap.add_argument("--monitor-top", type=int, default=5, metavar="N",
                     help="features named on the monitor line, by falling share outside the train band (default 5)")
+    ap.add_argument("--incidents", action="store_true",
+                    help="group the flagged rows into incidents: m of the last w rows, runs joined across short gaps")
+    ap.add_argument("--incident-window", type=int, default=64, metavar="W",
+                    help=f"rows the alarm count looks back over (1..{INCIDENT_MAX_WINDOW}; default 64)")
+    ap.add_argument("--incident-min", default="auto", metavar="M|auto",
+                    help="flagged rows in the window that make a row hot (1..W), or auto: from --incident-tail")
+    ap.add_argument("--incident-tail", type=float, default=1e-6, metavar="P",
+                    help="auto: the chance of a hot row under independent benign flags stays at or below P")
+    ap.add_argument("--incident-hold", type=int, default=None, metavar="H",
+                    help=f"hot rows at most H other rows apart share an incident (0..{INCIDENT_MAX_HOLD}; default W)")
     ns = ap.parse_args(argv)
+    if not 1 <= ns.incident_window <= INCIDENT_MAX_WINDOW:
+        ap.error(f"--incident-window takes 1..{INCIDENT_MAX_WINDOW}")
+    hold = ns.incident_window if ns.incident_hold is None else ns.incident_hold
+    if not 0 <= hold <= INCIDENT_MAX_HOLD:
+        ap.error(f"--incident-hold takes 0..{INCIDENT_MAX_HOLD}")
+    if not 0.0 < ns.incident_tail < 1.0:
+        ap.error("--incident-tail takes a probability between 0 and 1")
+    if ns.incident_min != "auto":
+        try:
+            ns.incident_min = int(ns.incident_min)
+        except ValueError:
+            ap.error("--incident-min takes a count or auto")
+        if not 1 <= ns.incident_min <= ns.incident_window:
+            ap.error("--incident-min takes 1..W (the window) or auto")
     if ns.monitor_top < 0:
         ap.error("--monitor-top takes a count >= 0")
     if ns.explain is not None and not 1 <= ns.explain <= EXPLAIN_MAX_K:
@@ -77,8 +116,17 @@ def main(argv=None) -> int:
     eng = make_engine(ns.backend, det.dims, device)
     # with --monitor two calls read the rows: on a GPU engine they are uploaded once, ahead of both
     shared = torch.from_numpy(rows).to(eng.device) if ns.monitor and eng.device.type == "cuda" else rows
+    min_alarms = ns.incident_min
+    if ns.incidents and min_alarms == "auto":
+        if not 0.0 <= det.detect_quantile <= 1.0:
+            ap.error("--incident-min auto needs the detector's detect_quantile; give a count")
+        min_alarms = incident_min_alarms(ns.incident_window, 1.0 - det.detect_quantile, ns.incident_tail)
+    inc = None
     t0 = time.perf_counter()
-    scores, flags, alarms = eng.score_rows([det], [shared])[0]
+    if ns.incidents:
+        scores, flags, alarms, inc = eng.score_incidents([det], [shared], ns.incident_window, min_alarms, hold)[0]
+    else:
+        scores, flags, alarms = eng.score_rows([det], [shared])[0]
     dt = time.perf_counter() - t0
     extra, tail = {}, ""
     if ns.explain is not None:
@@ -89,6 +137,9 @@ def main(argv=None) -> int:
         rep = eng.monitor_rows([det], [shared])[0]
         extra.update({"monitor_" + k: np.asarray(v) for k, v in dataclasses.asdict(rep).items() if v is not None})
         monitor_line = monitor_summary(det, rep, ns.monitor_top)
+    if inc is not None:
+        extra.update({"incident_" + k: getattr(inc, k) for k in ("start", "end", "alarms", "peak_row", "peak_score")})
+        extra["incident_params"] = np.array([inc.window, inc.min_alarms, inc.hold], dtype=np.int64)
     if ns.output:
         with open(ns.output, "wb") as f:
             np.savez(f, scores=scores, flags=flags, alarms=np.array(alarms, dtype=np.int64),
@@ -99,6 +150,9 @@ def main(argv=None) -> int:
           f"rows_per_s {rate:.1f}{tail}")
     if monitor_line is not None:
         print(monitor_line)
+    if inc is not None:
+        print(f"incidents: count {inc.count} rows_covered {inc.rows_covered} longest {inc.longest} "
+              f"hot_rows {inc.hot_rows} window {inc.window} min {inc.min_alarms} hold {inc.hold}")
     return 0
 
 

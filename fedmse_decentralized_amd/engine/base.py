@@ -319,6 +319,35 @@ class Engine:
         the summation order and is reported back."""
         raise NotImplementedError
 
+    def incidents(self, flags: Sequence, scores: Sequence, window: int, min_alarms: int, hold: int = 0) -> List:
+        """Group row-level alarms into incidents (README "Incidents").  One
+        ``(flags[i], scores[i])`` pair per item: vectors of one length ``n_i``
+        (numpy arrays or tensors on any device; the lengths may differ within
+        a call), rows in time order; a non-zero flag counts as 1, scores are
+        cleaned (NaN -> 0, +-inf -> +-DBL_MAX).  A row is hot when at least
+        ``min_alarms`` of the last ``window`` rows are flagged; hot rows with
+        at most ``hold`` other rows between them form one incident.  Returns
+        per item a ``deploy.detector.Incidents`` of numpy arrays: ``start``,
+        ``end``, ``alarms``, ``peak_row`` int64 [k], ``peak_score`` float64
+        [k], and the totals ``hot_rows``, ``count``, ``rows_covered``,
+        ``longest``.  An item without rows gives an empty one.  ``window``
+        outside 1..4096, ``min_alarms`` outside 1..window, ``hold`` outside
+        0..4096, lengths that differ and inputs that are no vectors raise
+        ValueError."""
+        raise NotImplementedError
+
+    def score_incidents(self, detectors: Sequence, rows: Sequence, window: int, min_alarms: int,
+                        hold: int = 0) -> List[tuple]:
+        """``score_rows`` and ``incidents`` of its flags and scores in one call:
+        per detector ``(scores, flags, alarms, incidents)``, the first three
+        exactly what ``score_rows`` returns."""
+        from ..deploy.detector import check_incident_params
+
+        check_incident_params(window, min_alarms, hold)
+        res = self.score_rows(detectors, rows)
+        inc = self.incidents([r[1] for r in res], [r[0] for r in res], window, min_alarms, hold)
+        return [(r[0], r[1], r[2], i) for r, i in zip(res, inc)]
+
     def standardize_ddof1(self, x: torch.Tensor) -> torch.Tensor:
         """(x - mean) / (std_ddof1 + 1e-8) over the real D columns
         (`src/Trainer/client_trainer.py:220-223`); the padded columns of the

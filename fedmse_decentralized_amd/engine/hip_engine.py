@@ -28,6 +28,9 @@
 * ``monitor_rows``  -> ``fedmx_monitor_rows`` (deployed detectors: per-feature statistics of the
                        standardised rows, alarm count and score histogram in one launch plus
                        the fold of the block partials; not in the reference)
+* ``incidents``     -> ``fedmx_incidents`` (alarms grouped into incidents: mark, scan, emit, peak
+                       and finish launches of fedmx_incident.hip; ``score_incidents`` runs them
+                       behind ``fedmx_score_rows`` on the same stream; not in the reference)
 * ``weighted_sum``  -> ``fedmx_weighted_sum`` -- src/Trainer/client_trainer.py:107-130
 * ``robust_aggregate`` -> ``fedmx_robust_agg`` (trimmed mean / median; not in the reference)
 * ``krum_aggregate`` -> ``fedmx_krum_agg`` (Krum / Multi-Krum; not in the reference)
@@ -377,6 +380,93 @@ class HipEngine(Engine):
                 a = int(counts[i])
                 h = hists[i, :base.score_edges.shape[0] + 1].copy() if base is not None else None
             out.append(drift_report(det, n, rpb, *stats, a, h))
+        return out
+
+    def _incident_inputs(self, flags, scores):
+        """One ``(flags, scores)`` item as contiguous uint8 / float64 vectors on
+        the device (a non-zero flag of any type becomes 1)."""
+        def dev(v):
+            return v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))
+
+        f, s = dev(flags), dev(scores)
+        _hip.check_incident_rows(f.shape, s.shape)
+        if f.dtype != torch.uint8:
+            f = (f != 0).to(torch.uint8)
+        return f.to(self.device).contiguous(), s.to(self.device, torch.float64).contiguous()
+
+    def _incident_results(self, res, sizes, w, m, h):
+        """The ``Incidents`` of ``_hip.incidents``' device results (the stream
+        is synchronised): the counts first, then that many entries per field."""
+        from ..deploy.detector import Incidents, empty_incidents
+
+        out = []
+        for o, n in zip(res, sizes):
+            if o is None:
+                out.append(empty_incidents(0, w, m, h))
+                continue
+            hot, k, covered, longest = (int(v) for v in o["summary"].cpu().numpy())
+            a = o["out"][:, :k].cpu().numpy()
+            p = o["peak"][:, :k].cpu().numpy()
+            out.append(Incidents(n=n, window=w, min_alarms=m, hold=h, start=a[0].copy(), end=a[1].copy(),
+                                 alarms=a[3].copy(), peak_row=p[1].copy(), peak_score=p[0].copy().view(np.float64),
+                                 hot_rows=hot, count=k, rows_covered=covered, longest=longest))
+        return out
+
+    def incidents(self, flags, scores, window, min_alarms, hold=0):
+        """The five launches of fedmx_incident.hip over every item's rows, one
+        synchronisation after them; an item without rows gets no workgroup and
+        a call without rows launches nothing."""
+        w, m, h = _hip.check_incident_params(window, min_alarms, hold)
+        if len(flags) != len(scores):
+            raise ValueError("incidents: one scores vector per flags vector")
+        pairs = [self._incident_inputs(f, s) for f, s in zip(flags, scores)]
+        sizes = [int(f.shape[0]) for f, _ in pairs]
+        if not any(sizes):
+            return self._incident_results([None] * len(pairs), sizes, w, m, h)
+        res = _hip.incidents([f for f, _ in pairs], [s for _, s in pairs], w, m, h)
+        self._rt.sync()
+        return self._incident_results(res, sizes, w, m, h)
+
+    def score_incidents(self, detectors, rows, window, min_alarms, hold=0):
+        """``score_rows``' launches, then the incident launches on the scores
+        and flags they left on the device: same stream, one synchronisation
+        at the end.  A knn detector's scores are cleaned and flagged on the
+        host as in ``score_rows`` (one synchronisation more) and uploaded."""
+        from ..deploy.detector import clean_and_flag
+
+        w, m, h = _hip.check_incident_params(window, min_alarms, hold)
+        if len(detectors) != len(rows):
+            raise ValueError("score_rows: one block of rows per detector")
+        xs = [self._rows_on_device(x, det) for det, x in zip(detectors, rows)]
+        sizes = [int(x.shape[0]) for x in xs]
+        live = [i for i, n in enumerate(sizes) if n > 0]
+        empty = (np.zeros(0, np.float64), np.zeros(0, np.uint8), 0)
+        if not live:
+            inc = self._incident_results([None] * len(xs), sizes, w, m, h)
+            return [empty + (i,) for i in inc]
+        states = [self._score_state(detectors[i]) for i in live]
+        res, alarms = _hip.score_rows([s for s, _ in states], [xs[i] for i in live])
+        knn = [j for j, (s, _) in enumerate(states) if s.kind == 0]
+        knn_scores = self._knn_scores_grouped([detectors[i] for i in live], [t for _, t in states],
+                                              [r[2] for r in res], knn)
+        host = {}
+        sc_dev, fl_dev = [r[0] for r in res], [r[1] for r in res]
+        if knn:
+            self._rt.sync()
+            for j in knn:
+                host[j] = clean_and_flag(knn_scores[j].cpu().numpy(), detectors[live[j]].threshold)
+                sc_dev[j] = torch.from_numpy(host[j][0]).to(self.device)
+                fl_dev[j] = torch.from_numpy(host[j][1]).to(self.device)
+        inc_dev = _hip.incidents(fl_dev, sc_dev, w, m, h)
+        self._rt.sync()
+        counts = alarms.cpu().numpy()
+        inc = self._incident_results(inc_dev, [sizes[i] for i in live], w, m, h)
+        out = [None] * len(xs)
+        for j, i in enumerate(live):
+            s, f, a = host[j] if j in host else (sc_dev[j].cpu().numpy(), fl_dev[j].cpu().numpy(), int(counts[j]))
+            out[i] = (s, f, a, inc[j])
+        for i in set(range(len(xs))) - set(live):
+            out[i] = empty + (self._incident_results([None], [0], w, m, h)[0],)
         return out
 
     def standardize_ddof1(self, x):

@@ -332,6 +332,18 @@ class TorchEngine(Engine):
             out.append(monitor_rows_numpy(det, x, rpb, engine=eng))
         return out
 
+    def incidents(self, flags, scores, window, min_alarms, hold=0):
+        from ..deploy.detector import check_incident_params, incidents_numpy
+
+        check_incident_params(window, min_alarms, hold)
+        if len(flags) != len(scores):
+            raise ValueError("incidents: one scores vector per flags vector")
+
+        def host(v):
+            return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+
+        return [incidents_numpy(host(f), host(s), window, min_alarms, hold) for f, s in zip(flags, scores)]
+
     def standardize_ddof1(self, x):
         D = self.dims.d_in
         xr = x[:, :D]

@@ -122,7 +122,17 @@ MONITOR_TOTAL_DTYPE = np.dtype([
     ("bad", "<i8", (MONITOR_COLS,)), ("out", "<i8", (MONITOR_COLS,)), ("mn", "<f4", (MONITOR_COLS,)),
     ("mx", "<f4", (MONITOR_COLS,)),
 ])
-from ..deploy.detector import EXPLAIN_MAX_K, MONITOR_MAX_EDGES, check_top_k, check_which  # noqa: E402  (the rule's one definition)
+# fedmx_incident.hip IncidentItem / IncidentSpanDesc
+INCIDENT_ITEM_DTYPE = np.dtype([
+    ("flags", "<u8"), ("scores", "<u8"), ("totals", "<u8"), ("offs", "<u8"), ("start", "<u8"), ("end", "<u8"),
+    ("pa", "<u8"), ("pb", "<u8"), ("key", "<u8"), ("enc", "<u8"), ("summary", "<u8"),
+    ("n", "<i4"), ("nspans", "<i4"), ("window", "<i4"), ("min_alarms", "<i4"), ("hold", "<i4"), ("kmax", "<i4"),
+])
+INCIDENT_SPAN_DTYPE = np.dtype([("item", "<i4"), ("span", "<i4")])
+INCIDENT_PHASES = {"mark": 1, "scan": 2, "emit": 4, "peak": 8, "finish": 16}
+INCIDENT_MAX_ITEMS = 65535   # the finish launch's grid.y
+from ..deploy.detector import (EXPLAIN_MAX_K, MONITOR_MAX_EDGES, check_incident_params, check_incident_rows,  # noqa: E402
+                               check_top_k, check_which, incident_bound)   # (the rules' one definition)
 
 
 class TrainArgs(ctypes.Structure):
@@ -242,6 +252,8 @@ def lib():
                 "fedmx_monitor_rows": [vp, i32, vp, i32, vp],
                 "fedmx_monitor_fold": [vp, i32, vp],
                 "fedmx_monitor_max_edges": [],
+                "fedmx_incidents": [vp, i32, vp, i32, i32, i32, vp],
+                "fedmx_incident_span_rows": [],
                 "fedmx_score_reduce": [vp, i32, i32, vp],
                 "fedmx_score_reduce_copy": [vp, i32, i32, vp, i32, vp],
                 "fedmx_broadcast_rows": [vp, vp, vp, i32, vp, i32, vp],
@@ -289,6 +301,9 @@ def lib():
             assert L.fedmx_monitor_partial_size() == MONITOR_PARTIAL_DTYPE.itemsize
             assert L.fedmx_monitor_total_size() == MONITOR_TOTAL_DTYPE.itemsize
             assert L.fedmx_monitor_max_edges() == MONITOR_MAX_EDGES
+            assert L.fedmx_incident_item_size() == INCIDENT_ITEM_DTYPE.itemsize
+            assert L.fedmx_incident_span_desc_size() == INCIDENT_SPAN_DTYPE.itemsize
+            assert L.fedmx_incident_span_rows() >= 8192 + 4098
             assert L.fedmx_seg_desc_size() == SEG_DTYPE.itemsize
             assert L.fedmx_train_args_size() == ctypes.sizeof(TrainArgs)
             sz = (ctypes.c_int * 4)()
@@ -1306,6 +1321,97 @@ def monitor_rows(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], row
         dptr, fptr = rt.desc.put(desc, fold)
         _check(lib().fedmx_monitor_rows(dptr, len(desc), fptr, len(fold), rt.stream), "fedmx_monitor_rows")
     return total, alarms, hist, lats, rpb, part
+
+
+# ---------------------------------------------------------------------------
+# incidents (fedmx_incident.hip)
+def incident_span_rows() -> int:
+    """Rows one incident workgroup owns (its halo comes on top)."""
+    return int(lib().fedmx_incident_span_rows())
+
+
+def incident_desc(flags: Sequence[torch.Tensor], scores: Sequence[torch.Tensor], window: int, min_alarms: int,
+                  hold: int, outs: Sequence[dict]):
+    """IncidentItem and IncidentSpanDesc arrays (fedmx_incident.hip): item i
+    groups ``flags[i]`` (uint8 [n], contiguous) with ``scores[i]`` (float64 [n])
+    into ``outs[i]``: ``out`` int64 [4, kmax] (start, end, and the two prefix
+    values; row 3 holds alarms after the finish pass), ``peak`` int64 [2, kmax]
+    zeroed (keys and coded rows; peak_score's bits and peak_row after it),
+    ``summary`` int64 [4] zeroed, ``ws`` int32 [2, nspans, 4], with ``kmax =
+    incident_bound(n, hold)``.  An item without rows gets no descriptor."""
+    w, m, h = check_incident_params(window, min_alarms, hold)
+    if not (len(flags) == len(scores) == len(outs)):
+        raise ValueError("incidents: one flags / scores / outputs entry per item")
+    S = incident_span_rows()
+    items, spans = [], []
+    for f, s, o in zip(flags, scores, outs):
+        n = check_incident_rows(f.shape, s.shape)
+        if f.dtype != torch.uint8 or s.dtype != torch.float64 or not f.is_contiguous() or not s.is_contiguous() \
+                or f.device != s.device:
+            raise ValueError("incidents: flags must be contiguous uint8 [n] and scores float64 [n] on one device")
+        if n == 0:
+            continue
+        kmax, nsp = incident_bound(n, h), -(-n // S)
+        out, peak, summary, ws = o["out"], o["peak"], o["summary"], o["ws"]
+        if out.dtype != torch.int64 or tuple(out.shape) != (4, kmax) or not out.is_contiguous() \
+                or peak.dtype != torch.int64 or tuple(peak.shape) != (2, kmax) or not peak.is_contiguous() \
+                or summary.dtype != torch.int64 or summary.numel() != 4 or not summary.is_contiguous() \
+                or ws.dtype != torch.int32 or tuple(ws.shape) != (2, nsp, 4) or not ws.is_contiguous() \
+                or ws.data_ptr() % 16 or any(t.device != f.device for t in (out, peak, summary, ws)):
+            raise ValueError(f"incidents: outputs must be int64 [4, {kmax}], [2, {kmax}] and [4] and a 16-byte "
+                             f"aligned int32 [2, {nsp}, 4] workspace on the flags' device")
+        d = np.zeros(1, dtype=INCIDENT_ITEM_DTYPE)
+        d["flags"], d["scores"] = f.data_ptr(), s.data_ptr()
+        d["totals"], d["offs"] = ws.data_ptr(), ws.data_ptr() + 16 * nsp
+        for j, name in enumerate(("start", "end", "pa", "pb")):
+            d[name] = out.data_ptr() + 8 * kmax * j
+        d["key"], d["enc"] = peak.data_ptr(), peak.data_ptr() + 8 * kmax
+        d["summary"] = summary.data_ptr()
+        d["n"], d["nspans"], d["window"], d["min_alarms"], d["hold"], d["kmax"] = n, nsp, w, m, h, kmax
+        sp = np.zeros(nsp, dtype=INCIDENT_SPAN_DTYPE)
+        sp["item"], sp["span"] = len(items), np.arange(nsp, dtype=np.int32)
+        items.append(d)
+        spans.append(sp)
+    if not items:
+        return np.zeros(0, dtype=INCIDENT_ITEM_DTYPE), np.zeros(0, dtype=INCIDENT_SPAN_DTYPE)
+    if len(items) > INCIDENT_MAX_ITEMS:
+        raise ValueError(f"incidents: at most {INCIDENT_MAX_ITEMS} items with rows per call")
+    return np.concatenate(items), np.concatenate(spans)
+
+
+def incidents(flags: Sequence[torch.Tensor], scores: Sequence[torch.Tensor], window: int, min_alarms: int,
+              hold: int = 0, phases: int = 31) -> List[Optional[dict]]:
+    """Group alarms into incidents (README "Incidents"): the mark, scan, emit,
+    peak and finish launches of fedmx_incident.hip over all items, on the
+    runtime's stream behind whatever produced ``flags`` and ``scores`` there.
+    Returns per item the ``incident_desc`` output tensors (None for an item
+    without rows), valid after the stream is synchronised: ``summary`` = (hot
+    rows, count, rows covered, longest); of ``out`` rows 0, 1, 3 and of
+    ``peak`` row 1 (peak_row) and row 0 (peak_score's bits) the first ``count``
+    entries.  Nothing launches when no item has rows."""
+    w, m, h = check_incident_params(window, min_alarms, hold)
+    S = incident_span_rows()
+    outs = []
+    for f, s in zip(flags, scores):
+        n = check_incident_rows(f.shape, s.shape)
+        if n == 0:
+            outs.append(None)
+            continue
+        dev, kmax = f.device, incident_bound(n, h)
+        outs.append({"out": torch.empty(4, kmax, dtype=torch.int64, device=dev),
+                     "peak": torch.zeros(2, kmax, dtype=torch.int64, device=dev),
+                     "summary": torch.zeros(4, dtype=torch.int64, device=dev),
+                     "ws": torch.empty(2, -(-n // S), 4, dtype=torch.int32, device=dev)})
+    live = [i for i, o in enumerate(outs) if o is not None]
+    if not live:
+        return outs
+    items, spans = incident_desc([flags[i] for i in live], [scores[i] for i in live], w, m, h,
+                                 [outs[i] for i in live])
+    rt = runtime(flags[live[0]].device)
+    iptr, sptr = rt.desc.put(items, spans)
+    _check(lib().fedmx_incidents(iptr, len(items), sptr, len(spans), int(items["kmax"].max()), int(phases),
+                                 rt.stream), "fedmx_incidents")
+    return outs
 
 
 def launch_score_rows(desc_dev: torch.Tensor, n: int, device):

@@ -415,6 +415,100 @@ def monitor_rows_timings(args) -> dict:
     return out
 
 
+def incidents_timings(args) -> dict:
+    """``--incidents``: the incident launches (fedmx_incident.hip) over the
+    ``--score-n`` raw float64 rows of ``--score-rows`` (same generator, the AE
+    detector), at window 64, hold 64 and the ``auto`` minimum for a 0.05 flag
+    rate, with the threshold at the score quantile that flags 5 % and 50 % of
+    the rows.  Event-timed with flags and scores on the device: the whole call
+    (two allocations, five launches) and the passes as cumulative prefixes of
+    the launch sequence, beside score_rows_kernel on the same rows; wall clock
+    from host rows to host results: ``HipEngine.score_incidents`` beside
+    ``HipEngine.score_rows`` followed by ``incidents_numpy`` on the host."""
+    from fedmse_decentralized_amd.deploy.detector import Detector, incident_min_alarms, incidents_numpy
+
+    dev = torch.device("cuda", 0)
+    dims = DEFAULT_DIMS
+    n = args.score_n
+    raws = generate_federation(SyntheticSpec(kind="nbaiot", n_clients=1, seed=1))
+    clients, _ = prepare_federation(raws, 1234)
+    sc = dict(clients[0].meta["scaler"])
+    kind = sc.pop("kind")
+    pool = np.concatenate([raws[0].normal, raws[0].abnormal, raws[0].test_normal], 0)
+    rows = pool[np.random.default_rng(3).integers(0, pool.shape[0], size=n)].copy()
+    init, _ = init_client_params(1, 0)
+    eng = HipEngine(dims, dev)
+    det = Detector(dims=dims, model_type="autoencoder", params=init[0].numpy(), scaler_kind=kind, scaler=sc,
+                   threshold=0.5, detect_quantile=0.95)
+    rows_dev = torch.from_numpy(rows).to(dev)
+    w, h = 64, 64
+    m = incident_min_alarms(w, 0.05, 1e-6)
+    S = _hip.incident_span_rows()
+    out = {"incidents_n": n, "incidents_window": w, "incidents_min_alarms": m, "incidents_hold": h,
+           "incidents_span_rows": S, "incidents_workgroups": -(-n // S), "incidents_threads": 1024}
+    scores0 = eng.score_rows([det], [rows])[0][0]
+    state, _ = eng._score_state(det)
+    out["score_rows_us"] = score_us = timeit(lambda: _hip.score_rows([state], [rows_dev]), reps=args.reps)[0]
+    rt = _hip.runtime(dev)
+    L = _hip.lib()
+    reps = max(args.reps // 2, 5)
+    for name, density in (("d05", 0.05), ("d50", 0.5)):
+        det.threshold = float(np.quantile(scores0, 1.0 - density))
+        state, _ = eng._score_state(det)
+        (sc_dev, fl_dev, _), = _hip.score_rows([state], [rows_dev])[0]
+        rt.sync()
+        out[f"incidents_{name}_flag_share"] = float(fl_dev.sum().item()) / n
+        us = timeit(lambda: _hip.incidents([fl_dev], [sc_dev], w, m, h), reps=args.reps)[0]
+        out[f"incidents_{name}_call_us"] = us
+        out[f"incidents_{name}_call_vs_score_rows"] = us / score_us
+        # the passes: prefixes of the launch sequence over one descriptor set (the zeroing inside the timed span)
+        o, = _hip.incidents([fl_dev], [sc_dev], w, m, h)
+        items, spans = _hip.incident_desc([fl_dev], [sc_dev], w, m, h, [o])
+        iptr, sptr = rt.desc.put(items, spans)
+        kmax = int(items["kmax"].max())
+
+        def run(phases):
+            o["peak"].zero_()
+            o["summary"].zero_()
+            _hip._check(L.fedmx_incidents(iptr, 1, sptr, len(spans), kmax, phases, rt.stream), "fedmx_incidents")
+
+        prev = 0.0
+        for pname, mask in (("mark", 1), ("scan", 3), ("emit", 7), ("peak", 15), ("finish", 31)):
+            t = timeit(lambda: run(mask), reps=args.reps)[0]
+            out[f"incidents_{name}_{pname}_us"] = t - prev
+            prev = t
+        out[f"incidents_{name}_launches_us"] = prev
+        out[f"incidents_{name}_launches_vs_score_rows"] = prev / score_us
+        wall = {"device": [], "host": []}
+        res = {}
+        for i in range(reps + 1):
+            for path, fn in (("device", lambda: eng.score_incidents([det], [rows], w, m, h)[0]),
+                             ("host", lambda: (lambda r: r + (incidents_numpy(r[1], r[0], w, m, h),))(
+                                 eng.score_rows([det], [rows])[0]))):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res[path] = fn()
+                torch.cuda.synchronize()
+                if i:
+                    wall[path].append(time.perf_counter() - t0)
+        a, b = res["device"][3], res["host"][3]
+        out[f"incidents_{name}_count"] = a.count
+        out[f"incidents_{name}_rows_covered"] = a.rows_covered
+        out[f"incidents_{name}_equal_host"] = bool(all(
+            getattr(a, k).tobytes() == getattr(b, k).tobytes() for k in ("start", "end", "alarms", "peak_row", "peak_score"))
+            and (a.hot_rows, a.count, a.rows_covered, a.longest) == (b.hot_rows, b.count, b.rows_covered, b.longest))
+        out[f"score_incidents_{name}_host_to_host_ms"] = float(np.median(wall["device"])) * 1e3
+        out[f"score_rows_plus_numpy_{name}_host_to_host_ms"] = float(np.median(wall["host"])) * 1e3
+        t0 = time.perf_counter()
+        incidents_numpy(res["host"][1], res["host"][0], w, m, h)
+        out[f"incidents_numpy_{name}_ms"] = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    eng.score_rows([det], [rows])
+    torch.cuda.synchronize()
+    out["score_rows_host_to_host_ms"] = (time.perf_counter() - t0) * 1e3
+    return out
+
+
 def auc_large_timings(args) -> dict:
     """``--auc-large``: the multi-workgroup AUC path (fedmx_auc_large.hip)
     beside the host fallback it replaces, on the same tensors.  Per shape:
@@ -489,6 +583,9 @@ def main():
     p.add_argument("--monitor-rows", action="store_true", help="only the drift-monitoring timings "
                    "(monitor_rows_kernel + monitor_fold_kernel over --score-n raw rows, AE and CEN, beside "
                    "score_rows_kernel on the same rows and host numpy computing the feature statistics)")
+    p.add_argument("--incidents", action="store_true", help="only the incident-grouping timings (the launches of "
+                   "fedmx_incident.hip over --score-n rows at flag densities 0.05 and 0.5, beside score_rows_kernel "
+                   "on the same rows and score_rows + incidents_numpy on the host)")
     p.add_argument("--monitor-kernels-only", action="store_true", help="with --monitor-rows: only the event-timed "
                    "launches (to compare builds of the kernel library)")
     p.add_argument("--score-n", type=int, default=1_000_000)
@@ -504,9 +601,10 @@ def main():
     p.add_argument("--reps", type=int, default=20)
     p.add_argument("--train-only", action="store_true", help="only the training-kernel timings (A/B of builds)")
     args = p.parse_args()
-    if args.score_rows or args.auc_large or args.explain_rows or args.monitor_rows:
+    if args.score_rows or args.auc_large or args.explain_rows or args.monitor_rows or args.incidents:
         out = (score_rows_timings if args.score_rows else explain_rows_timings if args.explain_rows
-               else monitor_rows_timings if args.monitor_rows else auc_large_timings)(args)
+               else monitor_rows_timings if args.monitor_rows else incidents_timings if args.incidents
+               else auc_large_timings)(args)
         print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
         return
     dev = torch.device("cuda", 0)
