@@ -839,3 +839,192 @@ def incident_min_alarms(window, rate, tail) -> int:
             break
         best = j
     return min(best, w)
+
+
+# ---------------------------------------------------------------------------
+# what an incident is about (README "Incident signatures")
+SIGNATURE_MAX_INCIDENTS = 4096
+SIGNATURE_TILE = 16
+SIGNATURE_WAVES = 4
+
+
+@dataclass
+class Signatures:
+    """What ``Engine.incident_signatures`` returns per detector (numpy).  The
+    first block is what the rule fixes to the bit; the second is derived from
+    it on the host in float64 (``signatures_report``)."""
+    incidents: np.ndarray     # int64 [s]: the summarised incidents, indices into the Incidents result
+    rows: np.ndarray          # int64 [s]: flagged rows inside [start, end] of each
+    block_rows: int
+    err_sum: np.ndarray       # float64 [s, D]: sum of fp32(r * r) over those rows, per feature
+    resid_sum: np.ndarray     # float64 [s, D]: sum of r = y - x
+    bad: np.ndarray           # int64 [s, D]: rows whose fp32(r * r) is NaN or +-inf (in neither sum)
+    idx: np.ndarray           # int32 [s, K]: features by falling err_sum, equal ones by rising index; -1 unused
+    share: np.ndarray         # float64 [s, K]: err_sum[idx] / sum of the incident's err_sum (NaN: zero total)
+    mean_resid: np.ndarray    # float64 [s, K]: resid_sum[idx] / max(rows - bad[idx], 1)
+
+    def similarity(self) -> np.ndarray:
+        """float64 [s, s]: the cosines between the incidents' ``err_sum`` rows
+        (NaN where a row is all zero)."""
+        e = self.err_sum
+        with np.errstate(all="ignore"):
+            norm = np.sqrt(np.sum(e * e, axis=1))
+            return (e @ e.T) / (norm[:, None] * norm[None, :])
+
+
+def check_signature_which(which, count: int) -> np.ndarray:
+    """The summarised incidents as int64 [s]: ``which`` (strictly rising
+    indices in ``[0, count)``) or, for None, ``0..count-1``; at most
+    SIGNATURE_MAX_INCIDENTS of them."""
+    if which is None:
+        w = np.arange(count, dtype=np.int64)
+    else:
+        if torch.is_tensor(which):
+            which = which.detach().cpu().numpy()
+        w = np.asarray(which)
+        if w.ndim != 1 or (w.size and w.dtype.kind not in "iu"):
+            raise ValueError(f"incident_signatures: which must be a vector of incident indices, got {w.dtype} "
+                             f"{w.shape}")
+        w = w.astype(np.int64)
+        if w.size and (int(w.min()) < 0 or int(w.max()) >= count):
+            raise ValueError(f"incident_signatures: which must lie in [0, {count})")
+        if np.any(np.diff(w) <= 0):
+            raise ValueError("incident_signatures: which must be strictly rising")
+    if w.shape[0] > SIGNATURE_MAX_INCIDENTS:
+        raise ValueError(f"incident_signatures: at most {SIGNATURE_MAX_INCIDENTS} incidents per call, got "
+                         f"{w.shape[0]}")
+    return w
+
+
+def signature_list(flags, incidents: Incidents, which=None):
+    """Step 1 of the signature rule: ``(L int64 [m], seg int32 [m], rows int64
+    [s])``.  ``L``: the rising rows ``i`` with ``flags[i] != 0`` inside
+    ``[start_k, end_k]`` of a chosen incident ``k``; ``seg[p]``: the position
+    in ``which`` of ``L[p]``'s incident; ``rows[j]``: how many entries incident
+    ``which[j]`` has.  ``which``: ``check_signature_which``."""
+    f = np.asarray(flags)
+    if f.ndim != 1 or f.shape[0] != incidents.n:
+        raise ValueError(f"incident_signatures: flags must be a vector of the incidents' {incidents.n} rows, got "
+                         f"shape {f.shape}")
+    w = check_signature_which(which, incidents.count)
+    s, n = int(w.shape[0]), int(f.shape[0])
+    # the chosen incident of every row (-1: none): the incidents' ranges are disjoint
+    step = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(step, incidents.start[w], np.arange(1, s + 1, dtype=np.int64))
+    np.add.at(step, incidents.end[w] + 1, -np.arange(1, s + 1, dtype=np.int64))
+    owner = np.cumsum(step[:n]) - 1
+    L = np.flatnonzero((f != 0) & (owner >= 0)).astype(np.int64)
+    seg = owner[L].astype(np.int32)
+    return L, seg, np.bincount(seg, minlength=s).astype(np.int64)
+
+
+def signature_sums(resid: np.ndarray, seg: np.ndarray, s: int, block_rows: int):
+    """Steps 3 and 4 of the signature rule on fp32 residual rows ``[m, D]``
+    (one per list position) and their incidents' positions ``seg`` (rising, in
+    ``[0, s)``): ``(err_sum float64 [s, D], resid_sum float64 [s, D], bad int64
+    [s, D])``.  Every stream (block b, wave w: the block's 16-position tiles
+    w, w + 4, ... in rising order) is accumulated position by position into
+    the partial of (b, incident, w) (all streams side by side, one position of
+    each per step; pair (b, j) in slot b + j), then each pair's streams fold in
+    wave order and each incident's blocks in block order."""
+    R = check_block_rows(block_rows)
+    r = np.asarray(resid, dtype=np.float32)
+    if r.ndim != 2:
+        raise ValueError(f"residual rows must be [m, D], got {r.shape}")
+    m, D = r.shape
+    s = int(s)
+    sg = np.asarray(seg, dtype=np.int64)
+    if sg.shape != (m,) or (m and (int(sg.min()) < 0 or int(sg.max()) >= s or np.any(np.diff(sg) < 0))):
+        raise ValueError(f"seg must hold {m} rising incident positions in [0, {s})")
+    err, res, bad = np.zeros((s, D), np.float64), np.zeros((s, D), np.float64), np.zeros((s, D), np.int64)
+    if m == 0 or s == 0:
+        return err, res, bad
+    nb = -(-m // R)
+    W = SIGNATURE_WAVES
+    pe, pr = np.zeros((nb + s, W, D), np.float64), np.zeros((nb + s, W, D), np.float64)
+    pb = np.zeros((nb + s, W, D), np.int64)
+    blk = np.broadcast_to(np.arange(nb, dtype=np.int64)[:, None], (nb, W))
+    wv = np.broadcast_to(np.arange(W, dtype=np.int64)[None, :], (nb, W))
+    with np.errstate(all="ignore"):
+        for p in range(R // W):   # position in the stream
+            pos = blk * R + (W * (p // SIGNATURE_TILE) + wv) * SIGNATURE_TILE + p % SIGNATURE_TILE   # [nb, W]
+            live = pos < np.minimum(m, (blk + 1) * R)
+            if not live.any():
+                break
+            q = pos[live]
+            slot, w_ = blk[live] + sg[q], wv[live]   # (one slot per stream: blocks and incidents both rise)
+            t = r[q]
+            e = t * t
+            fin = np.isfinite(e)
+            ce, cr = pe[slot, w_], pr[slot, w_]
+            pe[slot, w_] = np.where(fin, ce + e.astype(np.float64), ce)
+            pr[slot, w_] = np.where(fin, cr + t.astype(np.float64), cr)
+            pb[slot, w_] += ~fin
+        # streams -> (block, incident): ((p0 + p1) + p2) + p3
+        E, S, B = pe[:, 0], pr[:, 0], pb[:, 0]
+        for k in range(1, W):
+            E, S, B = E + pe[:, k], S + pr[:, k], B + pb[:, k]
+        # blocks -> incident, in block order from +0.0
+        cnt = np.bincount(sg, minlength=s)
+        off = np.concatenate([np.zeros(1, np.int64), np.cumsum(cnt)])
+        first, last = off[:-1] // R, np.where(cnt > 0, (off[1:] - 1) // R, off[:-1] // R - 1)
+        j = np.arange(s, dtype=np.int64)
+        for k in range(int((last - first).max()) + 1 if s else 0):
+            on = first + k <= last
+            sl = first[on] + k + j[on]
+            err[on] = err[on] + E[sl]
+            res[on] = res[on] + S[sl]
+            bad[on] += B[sl]
+    return err, res, bad
+
+
+def signatures_report(incidents, rows, block_rows: int, err_sum, resid_sum, bad, top_k) -> Signatures:
+    """Step 5: the ``Signatures`` of the rule's results, with the derived
+    float64 values (one function for every engine)."""
+    k = check_top_k(top_k)
+    err = np.ascontiguousarray(err_sum, dtype=np.float64)
+    res = np.ascontiguousarray(resid_sum, dtype=np.float64)
+    bad = np.ascontiguousarray(bad, dtype=np.int64)
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    s, D = err.shape
+    kk = min(k, D)
+    idx = np.full((s, k), -1, dtype=np.int32)
+    share, mean = np.zeros((s, k), np.float64), np.zeros((s, k), np.float64)
+    if s:
+        # K rounds of "the largest left, the lowest feature among equals" (argmax: the first maximum); the sums
+        # are finite and not negative, so -inf marks a taken feature
+        left, every = err.copy(), np.arange(s)
+        order = np.zeros((s, kk), dtype=np.int64)
+        for i in range(kk):
+            order[:, i] = np.argmax(left, axis=1)
+            left[every, order[:, i]] = -np.inf
+        idx[:, :kk] = order
+        with np.errstate(all="ignore"):
+            share[:, :kk] = np.take_along_axis(err, order, axis=1) / err.sum(axis=1)[:, None]
+            live = np.maximum(rows[:, None] - np.take_along_axis(bad, order, axis=1), 1)
+            mean[:, :kk] = np.take_along_axis(res, order, axis=1) / live
+    return Signatures(incidents=np.ascontiguousarray(incidents, dtype=np.int64), rows=rows, block_rows=int(block_rows),
+                      err_sum=err, resid_sum=res, bad=bad, idx=idx, share=share, mean_resid=mean)
+
+
+def incident_signatures_numpy(detector: Detector, rows: np.ndarray, flags, incidents: Incidents, top_k: int,
+                              which=None, block_rows: Optional[int] = None, engine=None) -> Signatures:
+    """The signature rule, step by step, on the host (the oracle of the
+    kernels in fedmx_signature.hip and what ``TorchEngine.incident_signatures``
+    runs): ``signature_list``, ``explain_rows_numpy(dense=True, which=L)``'s
+    residuals, ``signature_sums``, ``signatures_report``.  ``block_rows``:
+    default ``score_rows_per_block`` of the list's length.  ``engine``: as in
+    ``explain_rows_numpy``."""
+    k = check_top_k(top_k)
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] != detector.dims.d_in or rows.shape[0] != incidents.n:
+        raise ValueError(f"rows must be [{incidents.n}, {detector.dims.d_in}], got {rows.shape}")
+    L, seg, cnt = signature_list(flags, incidents, which)
+    w = check_signature_which(which, incidents.count)
+    if block_rows is None:
+        from ..ops._hip import score_rows_per_block
+
+        block_rows = score_rows_per_block(L.shape[0])
+    R = check_block_rows(block_rows)
+    resid = explain_rows_numpy(detector, rows, k, which=L, dense=True, engine=engine).resid_full
+    return signatures_report(w, cnt, R, *signature_sums(resid, seg, w.shape[0], R), k)

@@ -3,7 +3,8 @@
     python -m fedmse_decentralized_amd.detect --detector PATH/detector.npz \\
         --input traffic.csv [--output alarms.npz] [--backend auto|hip|torch] [--explain K]
         [--monitor [--monitor-top N]]
-        [--incidents [--incident-window W] [--incident-min M|auto] [--incident-tail P] [--incident-hold H]]
+        [--incidents [--incident-window W] [--incident-min M|auto] [--incident-tail P] [--incident-hold H]
+         [--signatures N [--signature-top K]]]
 
 ``--input`` is one headerless CSV of raw feature rows (one column per model
 input) or a directory of them, read in sorted file-name order by the
@@ -39,6 +40,18 @@ rows_covered R longest L hot_rows H window W min M hold H`` follows, and
 ``incident_peak_row``, ``incident_peak_score`` and ``incident_params`` (window,
 min, hold).  Rows are in time order: a directory's files are concatenated in
 sorted name order and a window runs across file boundaries.
+
+``--signatures N`` (README "Incident signatures"; needs ``--incidents``) also
+says what the N incidents with the most alarms (equal counts: the smaller
+index; reported in rising index order) are about: per incident the
+``--signature-top`` (default 5) features with the largest summed squared
+residual over the incident's flagged rows, their share of it and their mean
+residual.  A line ``# signatures: incidents S top_k K incident k rows R
+d:share:mean_resid ...`` follows, and ``--output`` gains ``signature_incident``,
+``signature_rows``, ``signature_idx``, ``signature_share``,
+``signature_mean_resid``, ``signature_err_sum``, ``signature_resid_sum``,
+``signature_bad`` and ``signature_similarity`` (the cosines between the
+incidents' ``err_sum`` rows).
 """
 from __future__ import annotations
 
@@ -52,8 +65,8 @@ import numpy as np
 import torch
 
 from .data.csv import load_data
-from .deploy.detector import (EXPLAIN_MAX_K, INCIDENT_MAX_HOLD, INCIDENT_MAX_WINDOW, Detector, expected_raw,
-                              incident_min_alarms)
+from .deploy.detector import (EXPLAIN_MAX_K, INCIDENT_MAX_HOLD, INCIDENT_MAX_WINDOW, SIGNATURE_MAX_INCIDENTS, Detector,
+                              expected_raw, incident_min_alarms)
 from .engine import make_engine
 from .ops import _host
 
@@ -88,7 +101,19 @@ def main(argv=None) -> int:
                     help="auto: the chance of a hot row under independent benign flags stays at or below P")
     ap.add_argument("--incident-hold", type=int, default=None, metavar="H",
                     help=f"hot rows at most H other rows apart share an incident (0..{INCIDENT_MAX_HOLD}; default W)")
+    ap.add_argument("--signatures", type=int, default=None, metavar="N",
+                    help="with --incidents: per-feature residual profile of the N incidents with the most alarms")
+    ap.add_argument("--signature-top", type=int, default=5, metavar="K",
+                    help=f"features named per incident, by falling summed squared residual (1..{EXPLAIN_MAX_K}; "
+                         "default 5)")
     ns = ap.parse_args(argv)
+    if ns.signatures is not None:
+        if not ns.incidents:
+            ap.error("--signatures needs --incidents")
+        if not 1 <= ns.signatures <= SIGNATURE_MAX_INCIDENTS:
+            ap.error(f"--signatures takes 1..{SIGNATURE_MAX_INCIDENTS}")
+        if not 1 <= ns.signature_top <= EXPLAIN_MAX_K:
+            ap.error(f"--signature-top takes 1..{EXPLAIN_MAX_K}")
     if not 1 <= ns.incident_window <= INCIDENT_MAX_WINDOW:
         ap.error(f"--incident-window takes 1..{INCIDENT_MAX_WINDOW}")
     hold = ns.incident_window if ns.incident_hold is None else ns.incident_hold
@@ -115,7 +140,8 @@ def main(argv=None) -> int:
     device = "cuda" if ns.backend == "hip" or (ns.backend == "auto" and torch.cuda.is_available()) else "cpu"
     eng = make_engine(ns.backend, det.dims, device)
     # with --monitor two calls read the rows: on a GPU engine they are uploaded once, ahead of both
-    shared = torch.from_numpy(rows).to(eng.device) if ns.monitor and eng.device.type == "cuda" else rows
+    shared = torch.from_numpy(rows).to(eng.device) if (ns.monitor or ns.signatures is not None) \
+        and eng.device.type == "cuda" else rows
     min_alarms = ns.incident_min
     if ns.incidents and min_alarms == "auto":
         if not 0.0 <= det.detect_quantile <= 1.0:
@@ -140,6 +166,15 @@ def main(argv=None) -> int:
     if inc is not None:
         extra.update({"incident_" + k: getattr(inc, k) for k in ("start", "end", "alarms", "peak_row", "peak_score")})
         extra["incident_params"] = np.array([inc.window, inc.min_alarms, inc.hold], dtype=np.int64)
+    signature_line = None
+    if ns.signatures is not None:
+        sig = eng.incident_signatures([det], [shared], [flags], [inc], top_k=ns.signature_top,
+                                      which=[largest_incidents(inc, ns.signatures)])[0]
+        extra.update({"signature_incident": sig.incidents, "signature_rows": sig.rows, "signature_idx": sig.idx,
+                      "signature_share": sig.share, "signature_mean_resid": sig.mean_resid,
+                      "signature_err_sum": sig.err_sum, "signature_resid_sum": sig.resid_sum,
+                      "signature_bad": sig.bad, "signature_similarity": sig.similarity()})
+        signature_line = signature_summary(sig, ns.signature_top)
     if ns.output:
         with open(ns.output, "wb") as f:
             np.savez(f, scores=scores, flags=flags, alarms=np.array(alarms, dtype=np.int64),
@@ -153,7 +188,27 @@ def main(argv=None) -> int:
     if inc is not None:
         print(f"incidents: count {inc.count} rows_covered {inc.rows_covered} longest {inc.longest} "
               f"hot_rows {inc.hot_rows} window {inc.window} min {inc.min_alarms} hold {inc.hold}")
+    if signature_line is not None:
+        print(signature_line)
     return 0
+
+
+def largest_incidents(inc, count: int) -> np.ndarray:
+    """The ``count`` incidents with the most alarms (equal counts: the smaller
+    index), as rising indices."""
+    order = np.argsort(-inc.alarms, kind="stable")[:max(0, int(count))]
+    return np.sort(order).astype(np.int64)
+
+
+def signature_summary(sig, top_k: int) -> str:
+    """The ``# signatures:`` line: per summarised incident its index, its
+    flagged rows and ``feature:share:mean_resid`` of its leading features."""
+    parts = [f"# signatures: incidents {sig.incidents.shape[0]} top_k {int(top_k)}"]
+    for j, k in enumerate(sig.incidents):
+        feats = " ".join(f"{int(d)}:{sig.share[j, i]:.4g}:{sig.mean_resid[j, i]:.4g}"
+                         for i, d in enumerate(sig.idx[j]) if d >= 0)
+        parts.append(f"incident {int(k)} rows {int(sig.rows[j])} {feats}")
+    return " ".join(parts)
 
 
 def monitor_summary(det: Detector, rep, top: int) -> str:

@@ -348,6 +348,26 @@ class Engine:
         inc = self.incidents([r[1] for r in res], [r[0] for r in res], window, min_alarms, hold)
         return [(r[0], r[1], r[2], i) for r, i in zip(res, inc)]
 
+    def incident_signatures(self, detectors: Sequence, rows: Sequence, flags: Sequence, incidents: Sequence,
+                            top_k: int = 5, which: Optional[Sequence] = None,
+                            block_rows: Optional[int] = None) -> List:
+        """What each incident is about (README "Incident signatures").  Per
+        detector: the raw rows ``[n_i, D]`` as in ``score_rows``, their flags
+        (``[n_i]``; non-zero counts as 1), the ``deploy.detector.Incidents`` of
+        those flags and ``which[i]``, the strictly rising indices of the
+        incidents to summarise (None, or ``which`` None: all; at most 4096).
+        Returns per detector a ``deploy.detector.Signatures``: per summarised
+        incident the number of flagged rows inside it, per feature the float64
+        sums ``err_sum`` of ``fp32(r * r)`` and ``resid_sum`` of the residual
+        ``r = y - x`` over those rows in the rule's fixed order and the count
+        ``bad`` of rows left out (a NaN or infinite square), and derived from
+        them the ``top_k`` features by ``err_sum`` with their share of the
+        total and their mean residual.  ``block_rows`` (a multiple of 64; None:
+        ``score_rows_per_block`` of all list positions) fixes the summation
+        order and is reported back.  ``top_k`` outside 1..16, a bad ``which``
+        and rows or flags of the wrong shape raise ValueError."""
+        raise NotImplementedError
+
     def standardize_ddof1(self, x: torch.Tensor) -> torch.Tensor:
         """(x - mean) / (std_ddof1 + 1e-8) over the real D columns
         (`src/Trainer/client_trainer.py:220-223`); the padded columns of the

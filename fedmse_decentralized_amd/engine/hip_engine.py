@@ -31,6 +31,9 @@
 * ``incidents``     -> ``fedmx_incidents`` (alarms grouped into incidents: mark, scan, emit, peak
                        and finish launches of fedmx_incident.hip; ``score_incidents`` runs them
                        behind ``fedmx_score_rows`` on the same stream; not in the reference)
+* ``incident_signatures`` -> ``fedmx_incident_signatures`` (per incident and feature the float64 sums
+                       of the squared and signed residuals over the incident's flagged rows:
+                       ``incident_sig_kernel`` and ``incident_sig_fold_kernel``; not in the reference)
 * ``weighted_sum``  -> ``fedmx_weighted_sum`` -- src/Trainer/client_trainer.py:107-130
 * ``robust_aggregate`` -> ``fedmx_robust_agg`` (trimmed mean / median; not in the reference)
 * ``krum_aggregate`` -> ``fedmx_krum_agg`` (Krum / Multi-Krum; not in the reference)
@@ -468,6 +471,44 @@ class HipEngine(Engine):
         for i in set(range(len(xs))) - set(live):
             out[i] = empty + (self._incident_results([None], [0], w, m, h)[0],)
         return out
+
+    def incident_signatures(self, detectors, rows, flags, incidents, top_k=5, which=None, block_rows=None):
+        """The list of flagged rows inside the chosen incidents is formed on
+        the host from the flags and uploaded; then ``incident_sig_kernel`` over
+        every detector's list and ``incident_sig_fold_kernel`` behind it, one
+        synchronisation after them.  An item without a list position gets no
+        workgroup, and a call without one launches nothing."""
+        from ..deploy.detector import (check_block_rows, check_signature_which, check_top_k, signature_list,
+                                       signatures_report)
+
+        k = check_top_k(top_k)
+        which = list(which) if which is not None else [None] * len(detectors)
+        if not (len(rows) == len(flags) == len(incidents) == len(which) == len(detectors)):
+            raise ValueError("incident_signatures: one rows / flags / incidents (and which) entry per detector")
+        if not detectors:
+            return []
+        xs = [self._rows_on_device(x, det) for det, x in zip(detectors, rows)]
+        lists, segs, counts, picked = [], [], [], []
+        for x, f, inc, w in zip(xs, flags, incidents, which):
+            f = f.detach().cpu().numpy() if torch.is_tensor(f) else np.asarray(f)
+            if int(x.shape[0]) != inc.n:
+                raise ValueError(f"rows must be [{inc.n}, D], got {tuple(x.shape)}")
+            L, seg, cnt = signature_list(f, inc, w)
+            lists.append(L)
+            segs.append(seg)
+            counts.append(cnt)
+            picked.append(check_signature_which(w, inc.count))
+        rpb = check_block_rows(block_rows if block_rows is not None
+                               else _hip.score_rows_per_block(sum(int(L.shape[0]) for L in lists)))
+        if not any(L.shape[0] for L in lists):   # nothing to reduce: the rule's initial values
+            return [signatures_report(w, cnt, rpb, np.zeros((len(w), det.dims.d_in)), np.zeros((len(w), det.dims.d_in)),
+                                      np.zeros((len(w), det.dims.d_in), np.int64), k)
+                    for det, w, cnt in zip(detectors, picked, counts)]
+        offsets = [np.concatenate([np.zeros(1, np.int64), np.cumsum(cnt)]) for cnt in counts]
+        res = _hip.incident_signatures([self._score_state(det)[0] for det in detectors], xs, lists, segs, offsets, rpb)
+        self._rt.sync()
+        return [signatures_report(w, cnt, rpb, r["err_sum"].cpu().numpy(), r["resid_sum"].cpu().numpy(),
+                                  r["bad"].cpu().numpy(), k) for r, w, cnt in zip(res, picked, counts)]
 
     def standardize_ddof1(self, x):
         return _hip.standardize_ddof1(x.contiguous(), self.dims.d_in)

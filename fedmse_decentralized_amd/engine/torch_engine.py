@@ -344,6 +344,29 @@ class TorchEngine(Engine):
 
         return [incidents_numpy(host(f), host(s), window, min_alarms, hold) for f, s in zip(flags, scores)]
 
+    def incident_signatures(self, detectors, rows, flags, incidents, top_k=5, which=None, block_rows=None):
+        from ..deploy.detector import (check_block_rows, check_top_k, incident_signatures_numpy, signature_list)
+        from ..ops._hip import score_rows_per_block
+
+        check_top_k(top_k)
+        which = list(which) if which is not None else [None] * len(detectors)
+        if not (len(rows) == len(flags) == len(incidents) == len(which) == len(detectors)):
+            raise ValueError("incident_signatures: one rows / flags / incidents (and which) entry per detector")
+
+        def host(v):
+            return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+
+        xs, fs = [host(x) for x in rows], [host(f) for f in flags]
+        if block_rows is None:
+            block_rows = score_rows_per_block(sum(int(signature_list(f, inc, w)[0].shape[0])
+                                                  for f, inc, w in zip(fs, incidents, which)))
+        rpb = check_block_rows(block_rows)
+        out = []
+        for det, x, f, inc, w in zip(detectors, xs, fs, incidents, which):
+            eng = self if det.dims == self.dims else TorchEngine(det.dims, self.device)
+            out.append(incident_signatures_numpy(det, x, f, inc, top_k, which=w, block_rows=rpb, engine=eng))
+        return out
+
     def standardize_ddof1(self, x):
         D = self.dims.d_in
         xr = x[:, :D]

@@ -131,6 +131,22 @@ INCIDENT_ITEM_DTYPE = np.dtype([
 INCIDENT_SPAN_DTYPE = np.dtype([("item", "<i4"), ("span", "<i4")])
 INCIDENT_PHASES = {"mark": 1, "scan": 2, "emit": 4, "peak": 8, "finish": 16}
 INCIDENT_MAX_ITEMS = 65535   # the finish launch's grid.y
+# fedmx_signature.hip SigDesc / SigFoldDesc / SigPartial
+SIG_DTYPE = np.dtype([
+    ("params", "<u8"), ("raw", "<u8"), ("sc_a", "<u8"), ("sc_b", "<u8"), ("which", "<u8"), ("seg", "<u8"),
+    ("part", "<u8"),
+    ("nrows", "<i4"), ("d_in", "<i4"), ("hidden", "<i4"), ("latent", "<i4"), ("flags", "<i4"), ("block", "<i4"),
+    ("nslots", "<i4"), ("pad", "<i4"),
+])
+SIG_FOLD_DTYPE = np.dtype([
+    ("part", "<u8"), ("err_sum", "<u8"), ("resid_sum", "<u8"), ("bad", "<u8"),
+    ("seg", "<i4"), ("first", "<i4"), ("last", "<i4"), ("d_in", "<i4"),
+])
+SIG_WAVES = 4
+SIG_PARTIAL_DTYPE = np.dtype([
+    ("se", "<f8", (SIG_WAVES, MONITOR_COLS)), ("sr", "<f8", (SIG_WAVES, MONITOR_COLS)),
+    ("bad", "<u4", (SIG_WAVES, MONITOR_COLS)),
+])
 from ..deploy.detector import (EXPLAIN_MAX_K, MONITOR_MAX_EDGES, check_incident_params, check_incident_rows,  # noqa: E402
                                check_top_k, check_which, incident_bound)   # (the rules' one definition)
 
@@ -254,6 +270,7 @@ def lib():
                 "fedmx_monitor_max_edges": [],
                 "fedmx_incidents": [vp, i32, vp, i32, i32, i32, vp],
                 "fedmx_incident_span_rows": [],
+                "fedmx_incident_signatures": [vp, i32, vp, i32, vp],
                 "fedmx_score_reduce": [vp, i32, i32, vp],
                 "fedmx_score_reduce_copy": [vp, i32, i32, vp, i32, vp],
                 "fedmx_broadcast_rows": [vp, vp, vp, i32, vp, i32, vp],
@@ -304,6 +321,9 @@ def lib():
             assert L.fedmx_incident_item_size() == INCIDENT_ITEM_DTYPE.itemsize
             assert L.fedmx_incident_span_desc_size() == INCIDENT_SPAN_DTYPE.itemsize
             assert L.fedmx_incident_span_rows() >= 8192 + 4098
+            assert L.fedmx_sig_desc_size() == SIG_DTYPE.itemsize
+            assert L.fedmx_sig_fold_desc_size() == SIG_FOLD_DTYPE.itemsize
+            assert L.fedmx_sig_partial_size() == SIG_PARTIAL_DTYPE.itemsize
             assert L.fedmx_seg_desc_size() == SEG_DTYPE.itemsize
             assert L.fedmx_train_args_size() == ctypes.sizeof(TrainArgs)
             sz = (ctypes.c_int * 4)()
@@ -1411,6 +1431,128 @@ def incidents(flags: Sequence[torch.Tensor], scores: Sequence[torch.Tensor], win
     iptr, sptr = rt.desc.put(items, spans)
     _check(lib().fedmx_incidents(iptr, len(items), sptr, len(spans), int(items["kmax"].max()), int(phases),
                                  rt.stream), "fedmx_incidents")
+    return outs
+
+
+# ---------------------------------------------------------------------------
+# incident signatures (fedmx_signature.hip)
+def signature_desc(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], which, seg, offsets, part: torch.Tensor,
+                   outs: Sequence[dict], rows_per_block: int):
+    """SigDesc and SigFoldDesc arrays (fedmx_signature.hip): item i reduces the
+    residuals of the list ``which[i]`` (int32 [m] on the device: row indices
+    into ``rows[i]``, every entry in ``[0, n)``) per incident, ``seg[i]`` (int32
+    [m] on the device, non-decreasing, in ``[0, s)``) naming each position's;
+    ``offsets[i]`` (host int64 [s + 1]) are the incidents' first list positions
+    and ``m``.  ``outs[i]``: ``err_sum`` / ``resid_sum`` float64 [s, d_in] and
+    ``bad`` int64 [s, d_in].  ``part`` (uint8) holds ``blocks + s`` zeroed
+    SIG_PARTIAL_DTYPE slots per item with list positions, in item order.  Every
+    list is cut into blocks of ``rows_per_block`` positions, one workgroup
+    each; an item with ``m = 0`` gets no descriptor of either kind."""
+    if not (len(rows) == len(which) == len(seg) == len(offsets) == len(outs) == len(states)):
+        raise ValueError("incident_signatures: one rows / list / offsets / outputs entry per detector")
+    rpb = int(rows_per_block)
+    if rpb < 1 or rpb % SCORE_CHUNK_ROWS:
+        raise ValueError(f"incident_signatures: rows per block must be a positive multiple of {SCORE_CHUNK_ROWS}")
+    psz = SIG_PARTIAL_DTYPE.itemsize
+    parts, folds, slot0 = [], [], 0
+    for st, x, w, sg, off, o in zip(states, rows, which, seg, offsets, outs):
+        dims = st.dims
+        off = np.asarray(off, dtype=np.int64)
+        s, m = int(off.shape[0]) - 1, int(off[-1])
+        if x.dim() != 2 or x.shape[1] != dims.d_in or x.dtype not in (torch.float32, torch.float64) \
+                or not x.is_contiguous() or x.device != st.device:
+            raise ValueError(f"incident_signatures: rows must be contiguous float32 / float64 [n, {dims.d_in}] on "
+                             "the detector's device")
+        if dims.d_in > 127:   # column 127 carries the forward's bias input, not a residual (fedmx_explain.hip)
+            raise ValueError(f"incident_signatures: d_in {dims.d_in} reaches the padded layout's bias column")
+        if int(x.shape[0]) > np.iinfo(np.int32).max:
+            raise ValueError("incident_signatures: the list indexes at most 2^31 - 1 rows")
+        for t, name in ((w, "the list"), (sg, "its incidents")):
+            if t.dtype != torch.int32 or tuple(t.shape) != (m,) or not t.is_contiguous() or t.device != st.device:
+                raise ValueError(f"incident_signatures: {name} must be contiguous int32 [{m}] on the detector's device")
+        if s < 0 or off[0] != 0 or np.any(np.diff(off) < 0):
+            raise ValueError("incident_signatures: the incidents' list offsets must start at 0 and not fall")
+        for name, dt in (("err_sum", torch.float64), ("resid_sum", torch.float64), ("bad", torch.int64)):
+            t = o.get(name)
+            if t is None or t.dtype != dt or tuple(t.shape) != (s, dims.d_in) or not t.is_contiguous() \
+                    or t.device != st.device:
+                raise ValueError(f"incident_signatures: {name} must be contiguous {dt} [{s}, {dims.d_in}] on the "
+                                 "detector's device")
+        if m == 0:
+            continue
+        r0 = np.arange(0, m, rpb, dtype=np.int64)
+        nslots = len(r0) + s
+        if part.dtype != torch.uint8 or not part.is_contiguous() or part.numel() < (slot0 + nslots) * psz:
+            raise ValueError("incident_signatures: the workspace holds blocks + incidents partial slots per item")
+        base = part.data_ptr() + psz * slot0
+        d = np.zeros(len(r0), dtype=SIG_DTYPE)
+        esz = 8 if x.dtype == torch.float64 else 4
+        d["params"] = st.params.data_ptr()
+        d["raw"] = x.data_ptr()
+        d["sc_a"] = st.scaler.data_ptr()
+        d["sc_b"] = st.scaler.data_ptr() + 8 * dims.d_in
+        d["which"] = w.data_ptr() + 4 * r0
+        d["seg"] = sg.data_ptr() + 4 * r0
+        d["part"] = base
+        d["nrows"] = np.minimum(rpb, m - r0)
+        d["d_in"], d["hidden"], d["latent"] = dims.d_in, dims.hidden, dims.latent
+        d["flags"] = (SCORE_RAW_F64 if esz == 8 else 0) | (SCORE_MINMAX if st.minmax else 0)
+        d["block"] = np.arange(len(r0))
+        d["nslots"] = nslots
+        parts.append(d)
+        j = np.arange(s, dtype=np.int64)
+        f = np.zeros(s, dtype=SIG_FOLD_DTYPE)
+        f["part"] = base
+        for name in ("err_sum", "resid_sum", "bad"):
+            f[name] = o[name].data_ptr() + 8 * dims.d_in * j
+        f["seg"] = j
+        f["first"] = off[:-1] // rpb
+        f["last"] = np.where(off[1:] > off[:-1], (off[1:] - 1) // rpb, off[:-1] // rpb - 1)   # (none: last < first)
+        f["d_in"] = dims.d_in
+        folds.append(f)
+        slot0 += nslots
+    if not parts:
+        return np.zeros(0, dtype=SIG_DTYPE), np.zeros(0, dtype=SIG_FOLD_DTYPE)
+    return np.concatenate(parts), np.concatenate(folds)
+
+
+def incident_signatures(states: Sequence[ScoreState], rows: Sequence[torch.Tensor], lists, segs, offsets,
+                        rows_per_block: int) -> List[dict]:
+    """Per-incident residual sums of deployed detectors (README "Incident
+    signatures"): one ``incident_sig_kernel`` launch over all items' lists and
+    one ``incident_sig_fold_kernel`` launch behind it.  ``lists[i]`` / ``segs[i]``:
+    host integer arrays [m] (``deploy.detector.signature_list``); ``offsets[i]``:
+    host int64 [s + 1].  Returns per item a dict of device tensors, valid after
+    the stream is synchronised: ``err_sum`` / ``resid_sum`` float64 [s, d_in],
+    ``bad`` int64 [s, d_in] (zeros for an incident or an item without list
+    positions), and what must stay alive until then.  Nothing launches when no
+    item has a list position."""
+    dev = states[0].device
+    rt = runtime(dev)
+    wdev, sdev, outs, nslots = [], [], [], 0
+    for st, x, w, sg, off in zip(states, rows, lists, segs, offsets):
+        w = np.asarray(w, dtype=np.int64)
+        n, m, s = int(x.shape[0]), int(w.shape[0]), int(len(off)) - 1
+        sg = np.asarray(sg, dtype=np.int32)
+        if sg.shape != (m,) or (m and (int(w.min()) < 0 or int(w.max()) >= n or int(sg.min()) < 0
+                                       or int(sg.max()) >= s or np.any(np.diff(sg) < 0))):
+            raise ValueError(f"incident_signatures: the list must index [0, {n}) and its incidents rise within "
+                             f"[0, {s})")
+        wdev.append(torch.from_numpy(w.astype(np.int32)).to(dev))
+        sdev.append(torch.from_numpy(np.ascontiguousarray(sg)).to(dev))
+        outs.append({"err_sum": torch.zeros(s, st.dims.d_in, dtype=torch.float64, device=dev),
+                     "resid_sum": torch.zeros(s, st.dims.d_in, dtype=torch.float64, device=dev),
+                     "bad": torch.zeros(s, st.dims.d_in, dtype=torch.int64, device=dev)})
+        if m:
+            nslots += -(-m // int(rows_per_block)) + s
+    part = torch.zeros(max(nslots, 1) * SIG_PARTIAL_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    desc, fold = signature_desc(states, rows, wdev, sdev, offsets, part, outs, rows_per_block)
+    if len(desc) and len(fold):
+        dptr, fptr = rt.desc.put(desc, fold)
+        _check(lib().fedmx_incident_signatures(dptr, len(desc), fptr, len(fold), rt.stream),
+               "fedmx_incident_signatures")
+    for o, w, sg in zip(outs, wdev, sdev):
+        o["keep"] = (w, sg, part)
     return outs
 
 

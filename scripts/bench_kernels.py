@@ -509,6 +509,109 @@ def incidents_timings(args) -> dict:
     return out
 
 
+def signatures_timings(args) -> dict:
+    """``--signatures``: incident signatures (fedmx_signature.hip) over the
+    rows, detector and incident parameters of ``--incidents``, with the
+    threshold at the score quantile that flags 5 % and 50 % of the rows (and,
+    at 5 %, also with window 16, min 3, hold 0: many short incidents); the
+    incidents summarised are all of them, or the 4096 with the most alarms.
+    Event-timed with the list on the device: the two launches (the zeroing of
+    the partial slots inside the timed span).  Wall clock from host flags and
+    incidents to host results, with the raw rows on the host and already on the
+    device: ``HipEngine.incident_signatures`` beside the only other way to the
+    same numbers, ``HipEngine.explain_rows(dense=True, which=L)`` followed by
+    ``signature_sums`` and ``signatures_report`` on the host; both must give
+    equal bits."""
+    from fedmse_decentralized_amd.deploy.detector import (SIGNATURE_MAX_INCIDENTS, Detector, incident_min_alarms,
+                                                          signature_list, signature_sums, signatures_report)
+
+    dev = torch.device("cuda", 0)
+    dims = DEFAULT_DIMS
+    n = args.score_n
+    raws = generate_federation(SyntheticSpec(kind="nbaiot", n_clients=1, seed=1))
+    clients, _ = prepare_federation(raws, 1234)
+    sc = dict(clients[0].meta["scaler"])
+    kind = sc.pop("kind")
+    pool = np.concatenate([raws[0].normal, raws[0].abnormal, raws[0].test_normal], 0)
+    rows = pool[np.random.default_rng(3).integers(0, pool.shape[0], size=n)].copy()
+    init, _ = init_client_params(1, 0)
+    eng = HipEngine(dims, dev)
+    det = Detector(dims=dims, model_type="autoencoder", params=init[0].numpy(), scaler_kind=kind, scaler=sc,
+                   threshold=0.5, detect_quantile=0.95)
+    rows_dev = torch.from_numpy(rows).to(dev)
+    w, h = 64, 64
+    m = incident_min_alarms(w, 0.05, 1e-6)
+    out = {"signatures_n": n, "signatures_window": w, "signatures_min_alarms": m, "signatures_hold": h}
+    scores0 = eng.score_rows([det], [rows_dev])[0][0]
+    rt = _hip.runtime(dev)
+    reps = max(args.reps // 4, 3)
+    # (at a flag share of 0.05 the auto minimum finds no incident in these rows: window 16, min 3, hold 0 beside it)
+    for name, density, (cw, cm, ch) in (("d05", 0.05, (w, m, h)), ("d05_w16_m3_h0", 0.05, (16, 3, 0)),
+                                        ("d50", 0.5, (w, m, h))):
+        det.threshold = float(np.quantile(scores0, 1.0 - density))
+        _, flags, _, inc = eng.score_incidents([det], [rows_dev], cw, cm, ch)[0]
+        out[f"signatures_{name}_incidents_found"] = inc.count
+        which = np.sort(np.argsort(-inc.alarms, kind="stable")[:SIGNATURE_MAX_INCIDENTS]).astype(np.int64)
+        L, seg, cnt = signature_list(flags, inc, which)
+        s, R = int(which.shape[0]), _hip.score_rows_per_block(L.shape[0])
+        out.update({f"signatures_{name}_flag_share": float(flags.sum()) / n, f"signatures_{name}_incidents": s,
+                    f"signatures_{name}_list_rows": int(L.shape[0]), f"signatures_{name}_block_rows": R,
+                    f"signatures_{name}_workgroups": -(-int(L.shape[0]) // R)})
+        if not L.shape[0]:
+            continue
+        # the two launches alone: one descriptor set, the list and the results on the device
+        state, _ = eng._score_state(det)
+        offsets = np.concatenate([np.zeros(1, np.int64), np.cumsum(cnt)])
+        o, = _hip.incident_signatures([state], [rows_dev], [L], [seg], [offsets], R)
+        wdev, sdev, part = o["keep"]
+        desc, fold = _hip.signature_desc([state], [rows_dev], [wdev], [sdev], [offsets], part, [o], R)
+        dptr, fptr = rt.desc.put(desc, fold)
+
+        def launches():
+            part.zero_()
+            _hip._check(_hip.lib().fedmx_incident_signatures(dptr, len(desc), fptr, len(fold), rt.stream),
+                        "fedmx_incident_signatures")
+
+        out[f"signatures_{name}_launches_us"] = timeit(launches, reps=args.reps)[0]
+        out[f"signatures_{name}_partial_mb"] = part.numel() / 1e6
+        out[f"signatures_{name}_dense_residual_mb"] = 4.0 * L.shape[0] * dims.d_in / 1e6
+
+        def fused(x):
+            return eng.incident_signatures([det], [x], [flags], [inc], which=[which], block_rows=R)[0]
+
+        def composed(x):
+            l, sg, c = signature_list(flags, inc, which)
+            r = eng.explain_rows([det], [x], top_k=5, which=[l], dense=True)[0].resid_full
+            return signatures_report(which, c, R, *signature_sums(r, sg, s, R), 5)
+
+        for where, x in (("host_rows", rows), ("device_rows", rows_dev)):
+            wall = {"fused": [], "composed": []}
+            res = {}
+            for i in range(reps + 1):
+                for path, fn in (("fused", fused), ("composed", composed)):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    res[path] = fn(x)
+                    torch.cuda.synchronize()
+                    if i:
+                        wall[path].append(time.perf_counter() - t0)
+            a, b = res["fused"], res["composed"]
+            out[f"signatures_{name}_{where}_equal_bits"] = bool(
+                all(getattr(a, k).tobytes() == getattr(b, k).tobytes()
+                    for k in ("rows", "err_sum", "resid_sum", "bad", "idx", "share", "mean_resid")))
+            fm, cm = float(np.median(wall["fused"])) * 1e3, float(np.median(wall["composed"])) * 1e3
+            out[f"signatures_{name}_{where}_fused_ms"] = fm
+            out[f"signatures_{name}_{where}_explain_plus_host_sums_ms"] = cm
+            out[f"signatures_{name}_{where}_composed_over_fused"] = cm / fm
+        t0 = time.perf_counter()
+        r = eng.explain_rows([det], [rows_dev], top_k=5, which=[L], dense=True)[0].resid_full
+        out[f"signatures_{name}_explain_dense_device_rows_ms"] = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        signature_sums(r, seg, s, R)
+        out[f"signatures_{name}_host_sums_ms"] = (time.perf_counter() - t0) * 1e3
+    return out
+
+
 def auc_large_timings(args) -> dict:
     """``--auc-large``: the multi-workgroup AUC path (fedmx_auc_large.hip)
     beside the host fallback it replaces, on the same tensors.  Per shape:
@@ -586,6 +689,9 @@ def main():
     p.add_argument("--incidents", action="store_true", help="only the incident-grouping timings (the launches of "
                    "fedmx_incident.hip over --score-n rows at flag densities 0.05 and 0.5, beside score_rows_kernel "
                    "on the same rows and score_rows + incidents_numpy on the host)")
+    p.add_argument("--signatures", action="store_true", help="only the incident-signature timings (the two launches "
+                   "of fedmx_signature.hip over the flagged rows of --score-n rows at flag densities 0.05 and 0.5, and "
+                   "the whole call beside explain_rows(dense) + signature_sums on the host)")
     p.add_argument("--monitor-kernels-only", action="store_true", help="with --monitor-rows: only the event-timed "
                    "launches (to compare builds of the kernel library)")
     p.add_argument("--score-n", type=int, default=1_000_000)
@@ -601,10 +707,11 @@ def main():
     p.add_argument("--reps", type=int, default=20)
     p.add_argument("--train-only", action="store_true", help="only the training-kernel timings (A/B of builds)")
     args = p.parse_args()
-    if args.score_rows or args.auc_large or args.explain_rows or args.monitor_rows or args.incidents:
+    if args.score_rows or args.auc_large or args.explain_rows or args.monitor_rows or args.incidents \
+            or args.signatures:
         out = (score_rows_timings if args.score_rows else explain_rows_timings if args.explain_rows
                else monitor_rows_timings if args.monitor_rows else incidents_timings if args.incidents
-               else auc_large_timings)(args)
+               else signatures_timings if args.signatures else auc_large_timings)(args)
         print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
         return
     dev = torch.device("cuda", 0)
