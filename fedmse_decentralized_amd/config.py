@@ -90,6 +90,12 @@ class ExperimentConfig:
     # "krum" / "multi_krum": the share of the selected models assumed poisoned,
     # f = floor(ratio * k), at most (k - 3) // 2 (krum_counts)
     robust_trim_ratio: float = 0.2
+    # update type "geomed": smoothed Weiszfeld iterations towards the geometric
+    # median of the selected models (0..64; 0 is the mean over the rows without
+    # NaN / infinity) and the smoothing, a finite distance > 0 below which a
+    # model's weight stops growing (protocol/aggregation.py geomed_check)
+    geomed_iters: int = 3
+    geomed_nu: float = 1e-6
     # metric "detection": the alarm threshold is the smallest validation score
     # (the client's own held-back normal rows, under the evaluated model) with
     # at least this share of them at or below it; in (0, 1]
@@ -203,6 +209,9 @@ class ExperimentConfig:
         if isinstance(self.monitor_bins, bool) or not isinstance(self.monitor_bins, int) \
                 or not 2 <= self.monitor_bins <= 16:
             raise ValueError(f"monitor_bins must be an integer in 2..16, got {self.monitor_bins!r}")
+        from .protocol.aggregation import geomed_check
+
+        geomed_check(self.geomed_iters, self.geomed_nu)
         if self.export_baseline and not self.export_detectors:
             raise ValueError("export_baseline records the baseline in the exported bundles: it needs export_detectors")
 
@@ -257,10 +266,14 @@ _HELP = {
                        "fedmse_decentralized_amd.detect --monitor compares live traffic with it) (default false)",
     "monitor_bins": "--export-baseline: number of score bins of the baseline, 2..16 (default 10)",
     "knn_k": "latent scorer knn: which nearest train latent's distance is the score, 1..16 (default 5)",
-    "update_types": "any of: avg fedprox mse_avg fusion_avg trimmed_mean median krum multi_krum",
+    "update_types": "any of: avg fedprox mse_avg fusion_avg trimmed_mean median krum multi_krum geomed",
     "robust_trim_ratio": "share of the selected models assumed poisoned, in [0, 0.5): trimmed_mean drops that "
                          "fraction at each end of every coordinate's order, krum / multi_krum discard that "
                          "fraction of whole models by distance (default 0.2)",
+    "geomed_iters": "update type geomed: smoothed Weiszfeld iterations towards the geometric median of the "
+                    "selected models, 0..64 (0: the mean of the models without NaN / infinity; default 3)",
+    "geomed_nu": "update type geomed: smoothing of the Weiszfeld weights 1 / max(distance, nu), finite and > 0 "
+                 "(default 1e-6)",
 }
 
 

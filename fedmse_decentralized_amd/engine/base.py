@@ -230,6 +230,13 @@ class Engine:
         ``protocol/aggregation.py``), added in row order."""
         raise NotImplementedError
 
+    def geomed_aggregate(self, stack: torch.Tensor, iters: int, nu: float):
+        """[k, P] -> ([P], the k final weights as floats in row order): the
+        smoothed geometric median of the rows after ``iters`` Weiszfeld
+        iterations, weights 1 / max(distance, nu) normalised in f64, rows with
+        a NaN or an infinity weighted 0 (``protocol/aggregation.py``)."""
+        raise NotImplementedError
+
     def param_drift(self, hist: torch.Tensor, new: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
 

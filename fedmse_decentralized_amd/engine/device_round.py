@@ -21,6 +21,10 @@ can be *enqueued* instead:
                             krum / multi_krum only: pairwise distances, scores, the
                             kept rows' mean over the same rows; overwrites the
                             aggregate, kept mask into a mapped slot]
+    [geomed_step kernel x (geomed_iters + 2)
+                            geomed only: smoothed Weiszfeld iterations over the
+                            same rows; overwrites the aggregate, final weights
+                            into a mapped slot]
     verify_decide_kernel    fused: forward(agg, every hosted client's verification
                             data) [+ own model: thesis], MSE + drift reductions,
                             ModelVerifier / thesis rule (or centralised push),
@@ -63,7 +67,7 @@ import torch
 from ..eval.metrics import DETECT_METRICS, detection_fields
 from ..models.layout import P_PAD
 from ..ops import _hip
-from ..protocol.aggregation import KRUM_TYPES, ROBUST_TYPES, krum_counts, trim_count
+from ..protocol.aggregation import GEOMED_TYPES, KRUM_TYPES, ROBUST_TYPES, krum_counts, trim_count
 
 # fence-less device events for the kernel-to-kernel stream dependencies
 # ("0": torch events, which record with a system-scope fence)
@@ -100,7 +104,7 @@ def fast_path_supported(fed) -> Optional[str]:
         (cfg.protocol_variant == "code" or _thesis_fused_ok(fed),
          "thesis variant with verification rows beyond the fused kernel's LDS buffer"),
         (fed.update_type in ("avg", "fedprox", "mse_avg", "fusion_avg", "trimmed_mean", "median", "krum",
-                             "multi_krum"),
+                             "multi_krum", "geomed"),
          f"update type {fed.update_type}"),
         (cfg.metric in ("AUC", "classification", "time") + DETECT_METRICS, f"metric {cfg.metric}"),
         # dropped clients leave at least one selection per round (k >= 1: the
@@ -136,6 +140,7 @@ class LazyRoundResult:
     epochs_run = property(lambda self: self._get("epochs_run"))
     stop = property(lambda self: self._get("stop"))
     agg_kept = property(lambda self: self._get("agg_kept"))
+    agg_weights = property(lambda self: self._get("agg_weights"))
     detection = property(lambda self: self._get("detection"))
 
 
@@ -285,8 +290,16 @@ class DeviceRound:
         # krum / multi_krum: rule 0, then the three krum kernels overwrite the aggregate
         self.robust = fed.update_type in ROBUST_TYPES
         self.krum = fed.update_type in KRUM_TYPES
+        # geomed: rule 0, then the geomed_iters + 2 Weiszfeld launches overwrite the aggregate
+        self.geomed = fed.update_type in GEOMED_TYPES
         self.rule = 1 if fed.update_type == "mse_avg" else (
-            2 if (cfg.fedavg_sample_weighted or self.fusion) and not (self.robust or self.krum) else 0)
+            2 if (cfg.fedavg_sample_weighted or self.fusion) and not (self.robust or self.krum or self.geomed)
+            else 0)
+        if self.geomed:
+            # one workspace (two halves of block partials), sized once for the
+            # largest selection a round can make (k <= N)
+            self.geomed_ws = torch.empty(_hip.geomed_workspace_size(max(N, 1), P_PAD), dtype=torch.float64,
+                                         device=dev)
         if self.krum:
             # one workspace (distances, scores, kept positions), sized once for
             # the largest selection a round can make (k <= N)
@@ -628,6 +641,17 @@ class DeviceRound:
                 _hip.krum_aggregate(base, rows_ptr, k, kf, km, self.agg, state_ptr=self.state.data_ptr(),
                                     workspace=self.krum_ws, kept_out=kept_ptr)
                 rec["kept"] = kept_view
+            elif self.geomed:
+                # geomed: the Weiszfeld launches over the same rows and election
+                # state overwrite the plain mean (geomed_iters + 2 extra launches,
+                # paid by this rule only); the final weights land in a mapped
+                # slot read with the round's report
+                gw_ptr, gw_view = self.rt.out.take(np.float64, k)
+                gw_view[:] = -1.0
+                _hip.geomed_aggregate(base, rows_ptr, k, cfg.geomed_iters, cfg.geomed_nu, self.agg,
+                                      state_ptr=self.state.data_ptr(), workspace=self.geomed_ws,
+                                      weights_out=gw_ptr)
+                rec["gweights"] = gw_view
             rec["report"] = rep_view
         # the previous round's side work has read the snapshot / report buffers
         side = self.side_slots[rnd % len(self.side_slots)]
@@ -823,6 +847,12 @@ class DeviceRound:
             agg_kept = [c for c, kj in zip(rec["selected"], rec["kept"]) if int(kj) == 1]
             log.info(f"Aggregate keeps clients {[c + 1 for c in agg_kept]} of {[c + 1 for c in rec['selected']]} "
                      f"({fed.update_type})")
+        agg_weights = None
+        if aggregator is not None and "gweights" in rec:
+            from ..federation import geomed_log_line
+
+            agg_weights = [float(x) for x in rec["gweights"]]
+            log.info(geomed_log_line(rec["selected"], agg_weights, cfg.geomed_iters))
         verification = []
         if aggregator is not None and self.centralized:
             # centralised push: every client adopted the aggregate, nothing to report
@@ -872,7 +902,7 @@ class DeviceRound:
 
             stop = fed.early.update(metric_stats(metrics)[1])
         rec.update(aggregator=aggregator, metrics=metrics, verification=verification, epochs_run=epochs_local,
-                   stop=stop, agg_kept=agg_kept, detection=detection, done=True)
-        for key in ("handle", "snap_slot", "slot", "report", "kept", "detect", "_keep", "event", "eval_params", "eval_timing", "train_ev"):
+                   stop=stop, agg_kept=agg_kept, agg_weights=agg_weights, detection=detection, done=True)
+        for key in ("handle", "snap_slot", "slot", "report", "kept", "gweights", "detect", "_keep", "event", "eval_params", "eval_timing", "train_ev"):
             rec.pop(key, None)
         self.all_rounds.pop(rnd, None)

@@ -37,6 +37,8 @@
 * ``weighted_sum``  -> ``fedmx_weighted_sum`` -- src/Trainer/client_trainer.py:107-130
 * ``robust_aggregate`` -> ``fedmx_robust_agg`` (trimmed mean / median; not in the reference)
 * ``krum_aggregate`` -> ``fedmx_krum_agg`` (Krum / Multi-Krum; not in the reference)
+* ``geomed_aggregate`` -> ``fedmx_geomed_agg`` (geometric median by smoothed Weiszfeld iterations;
+                       not in the reference)
 
 Descriptor arrays are cached on the device for static work and streamed
 through a pinned ring otherwise; device->host traffic goes through a pinned
@@ -130,6 +132,11 @@ class HipEngine(Engine):
         kept = torch.empty(int(stack.shape[0]), dtype=torch.int32, device=stack.device)
         agg = _hip.krum_aggregate_stack(stack, int(f), int(m), kept_out=kept)
         return agg, [int(i) for i in torch.nonzero(kept).flatten().tolist()]
+
+    def geomed_aggregate(self, stack, iters, nu):
+        w = torch.empty(int(stack.shape[0]), dtype=torch.float64, device=stack.device)
+        agg = _hip.geomed_aggregate_stack(stack, iters, nu, weights_out=w)
+        return agg, [float(x) for x in w.tolist()]
 
     def param_drift(self, hist, new):
         return _hip.param_drift(hist, new, self._seg)

@@ -214,6 +214,72 @@ class TorchEngine(Engine):
             acc = acc + st[j]
         return acc / torch.tensor(float(m), dtype=torch.float32, device=dev), kept
 
+    def geomed_aggregate(self, stack, iters, nu):
+        from ..protocol.aggregation import geomed_check
+
+        iters, nu = geomed_check(iters, nu)
+        k, P = stack.shape
+        if k < 1 or P < 1:
+            raise ValueError(f"geomed_aggregate: a stack of {k} models of {P} values")
+        f64 = torch.float64
+        st = stack.detach().contiguous().to(device="cpu", dtype=torch.float32)
+        nb = -(-P // 256)
+        pad = torch.zeros(k, nb * 256, dtype=torch.float32)
+        pad[:, :P] = st
+        st64 = st.to(f64)
+        inf = float("inf")
+
+        def fold(p):   # eight folds p_l += p_{l+h}, h = 128 .. 1, over the last axis
+            h = 128
+            while h >= 1:
+                p = p[..., :h] + p[..., h:2 * h]
+                h //= 2
+            return p[..., 0]
+
+        def dist(z):   # step 1: the block sum of the squared fp32 differences
+            e = (pad if z is None else pad - z).to(f64)   # one fp32 rounding, then exact in f64
+            s = e * e
+            s[:, P:] = 0.0                                # the zero extension
+            q = fold(s.view(k, nb, 256))
+            d = torch.zeros(k, dtype=f64)
+            for b in range(nb):
+                d = d + q[:, b]
+            return torch.where(torch.isnan(d) | (d == inf), torch.full_like(d, inf), d)
+
+        def lane_sum(x):
+            C = -(-k // 256)
+            xp = torch.zeros(C * 256, dtype=f64)
+            xp[:k] = x
+            p = torch.zeros(256, dtype=f64)
+            for c in range(C):
+                p = p + xp[c * 256:(c + 1) * 256]
+            return float(fold(p))
+
+        d = dist(None)
+        beta = torch.where(d < inf, torch.ones_like(d), torch.zeros_like(d))
+        for t in range(iters + 1):
+            B = lane_sum(beta)
+            if B == 0.0:   # every row bad: the rule ends
+                z = torch.full((P,), 0x7FC00000, dtype=torch.int32).view(torch.float32)
+                w = torch.zeros(k, dtype=f64)
+                break
+            w = beta / torch.full_like(beta, B)   # (a tensor divisor: an IEEE division per element)
+            acc = torch.zeros(P, dtype=f64)
+            for i in range(k):
+                if float(beta[i]) != 0.0:
+                    acc = acc + w[i] * st64[i]
+            z = acc.to(torch.float32)
+            if t == iters:
+                break
+            zp = torch.zeros(nb * 256, dtype=torch.float32)
+            zp[:P] = z
+            d = dist(zp)
+            with np.errstate(all="ignore"):
+                r = torch.from_numpy(np.sqrt(d.numpy()))   # (torch.sqrt's vectorised f64 path is not correctly rounded)
+            beta = torch.where(d < inf, torch.ones_like(r) / torch.maximum(r, torch.full_like(r, nu)),
+                               torch.zeros_like(d))
+        return z.to(stack.device), [float(x) for x in w.tolist()]
+
     def param_drift(self, hist, new):
         a = padded_to_canonical(hist, self.dims)
         b = padded_to_canonical(new.unsqueeze(0), self.dims)

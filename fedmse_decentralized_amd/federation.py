@@ -42,7 +42,7 @@ from .models.layout import P_PAD, ModelDims
 from .models.reference import init_client_params
 from .parallel.comm import Comm, LoopbackComm
 from .parallel.sharding import ShardMap
-from .protocol.aggregation import KRUM_TYPES, ROBUST_TYPES, krum_counts, make_plan, trim_count
+from .protocol.aggregation import GEOMED_TYPES, KRUM_TYPES, ROBUST_TYPES, krum_counts, make_plan, trim_count
 from .protocol.early_stop import GlobalEarlyStop
 from .protocol.election import OneDraw, elect_aggregator, elect_majority, select_clients
 from .protocol.verification import ThesisVerifier, Verifier, VerifierState
@@ -140,10 +140,19 @@ class RoundResult:
     # krum / multi_krum: the clients whose models the aggregate holds, in
     # selection order (None for every other rule and when nobody was elected)
     agg_kept: Optional[List[int]] = None
+    # geomed: the final Weiszfeld weights of the selected models, in selection
+    # order (None for every other rule and when nobody was elected)
+    agg_weights: Optional[List[float]] = None
     # metric "detection" / "tpr_at_fpr": per client (arrays [N], identical on
     # every rank) threshold, tp, fp, fn, tn, precision, recall, f1, fpr at the
     # calibrated threshold (eval/metrics.py); None for every other metric
     detection: Optional[Dict[str, np.ndarray]] = None
+
+
+def geomed_log_line(selected, weights, iters) -> str:
+    """The round's info line of the geomed rule: clients and their weights."""
+    pairs = ", ".join(f"{c + 1}: {w:.6g}" for c, w in zip(selected, weights))
+    return f"Aggregate weights of clients {{{pairs}}} (geomed, {iters} iterations)"
 
 
 class _TableNoise:
@@ -466,11 +475,13 @@ class Federation:
 
         verification_results: List[Dict] = []
         agg_kept = None
+        agg_weights = None
         if aggregator is not None:
             if info:
                 log.info(f"Client {aggregator + 1} selected as aggregator")
             krum = self.update_type in KRUM_TYPES
-            robust = self.update_type in ROBUST_TYPES or krum
+            geomed = self.update_type in GEOMED_TYPES
+            robust = self.update_type in ROBUST_TYPES or krum or geomed
             with self.tel.phase("aggregate"):
                 if self.update_type == "mse_avg" and cfg.compat == "reference":
                     for _ in selected:          # calculate_mse_score per client (weights unused, Q3)
@@ -483,7 +494,8 @@ class Federation:
                         sim = self._fusion_similarity(selected)
                 ns = {c: self.clients[c].train.shape[0] for c in selected} if cfg.fedavg_sample_weighted else None
                 # (the robust rules are no (source, weight) plan: an order statistic per
-                # coordinate, or a distance-based choice of whole models)
+                # coordinate, a distance-based choice of whole models, or weights
+                # that depend on the models themselves)
                 plan = None if robust else make_plan(self.update_type, selected, aggregator, dev_mse, cfg.compat,
                                                      sim=sim, num_samples=ns, fusion_w=fw)
             with self.tel.phase("comm"):
@@ -495,6 +507,9 @@ class Federation:
                     agg_kept = [selected[i] for i in pos]
                     log.info(f"Aggregate keeps clients {[c + 1 for c in agg_kept]} of {[c + 1 for c in selected]} "
                              f"({self.update_type}, f = {f})")
+                elif geomed:
+                    agg, agg_weights = eng.geomed_aggregate(stack, cfg.geomed_iters, cfg.geomed_nu)
+                    log.info(geomed_log_line(selected, agg_weights, cfg.geomed_iters))
                 elif robust:
                     agg = eng.robust_aggregate(stack, trim_count(self.update_type, len(selected),
                                                                  cfg.robust_trim_ratio))
@@ -569,7 +584,7 @@ class Federation:
         self.round_idx += 1
         times = self.tel.end_round(round=rnd + 1, selected=len(selected), aggregator=aggregator)
         return RoundResult(rnd, list(selected), aggregator, metrics, verification_results, epochs_all, stop, times,
-                           agg_kept, detection)
+                           agg_kept, agg_weights, detection)
 
     def _verify_all(self, agg: torch.Tensor, version: int, aggregator: int, rnd: int) -> List[Dict]:
         """Every receiver verifies the broadcast aggregate (all N clients but the

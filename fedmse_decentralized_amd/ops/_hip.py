@@ -17,6 +17,7 @@ never a silent PyTorch fallback.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import threading
 from pathlib import Path
@@ -196,6 +197,8 @@ class DecideArgs(ctypes.Structure):
 VERIFY_MAX_ROWS = 4096   # rows of one receiver's verification data the fused kernel keeps in LDS
 ROBUST_MAX_K = 1024      # models one robust_agg_kernel tile ranks (elect_wsum's row table has the same bound)
 KRUM_MAX_K = 1024        # models the krum kernels rank in LDS (fedmx_krum.hip)
+GEOMED_MAX_K = 1024      # models whose weights geomed_step_kernel keeps in LDS (fedmx_geomed.hip)
+GEOMED_MAX_ITERS = 64    # Weiszfeld iterations of one geomed_aggregate (T + 2 launches)
 
 IPC_MAX_WORLD = 16
 IPC_MAX_CHUNKS = 64
@@ -252,6 +255,8 @@ def lib():
                 "fedmx_krum_agg": [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
                 "fedmx_krum_max_k": [],
                 "fedmx_krum_tile": [],
+                "fedmx_geomed_agg": [vp, vp, vp, vp, i32, i32, i32, ctypes.c_double, vp, vp, vp, vp],
+                "fedmx_geomed_max_k": [],
                 "fedmx_param_drift": [vp, i32, vp, vp, vp, vp],
                 "fedmx_standardize_lds": [vp, i32, i32, vp, vp],
                 "fedmx_cen_score": [vp, i32, vp],
@@ -335,6 +340,7 @@ def lib():
             assert L.fedmx_ipc_max_world() == IPC_MAX_WORLD and L.fedmx_ipc_max_chunks() == IPC_MAX_CHUNKS
             assert L.fedmx_robust_max_k() == ROBUST_MAX_K
             assert L.fedmx_krum_max_k() == KRUM_MAX_K
+            assert L.fedmx_geomed_max_k() == GEOMED_MAX_K
             assert L.fedmx_knn_max_k() == KNN_MAX_K
             _lib = L
     return _lib
@@ -1803,6 +1809,80 @@ def krum_aggregate_stack(stack: torch.Tensor, f: int, m: int, out: Optional[torc
     if out is None:
         out = torch.empty(st.shape[1], dtype=torch.float32, device=st.device)
     return krum_aggregate(st, None, int(st.shape[0]), f, m, out, **kw)
+
+
+def geomed_workspace_size(k: int, P: int) -> int:
+    """float64 elements of the geomed kernel's workspace for ``k`` models of
+    ``P`` values: two halves of block partials ``part[ceil(P / 256)][k]``
+    (successive launches read one and write the other)."""
+    return 2 * (-(-int(P) // 256)) * int(k)
+
+
+def _geomed_f64_out(name: str, t, k: int, device) -> int:
+    """Address of a float64 ``[k]`` result: a tensor on ``device``, a
+    device-visible address, or None."""
+    if isinstance(t, torch.Tensor):
+        if t.dtype != torch.float64 or t.numel() < k or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"geomed_aggregate: {name} must be a contiguous float64 [k] tensor on base's device")
+        return t.data_ptr()
+    return 0 if t is None else int(t)
+
+
+def geomed_aggregate(base: torch.Tensor, rows_ptr: Optional[int], k: int, iters: int, nu: float, out: torch.Tensor,
+                     state_ptr: int = 0, workspace: Optional[torch.Tensor] = None, weights_out=None,
+                     dist_out=None) -> torch.Tensor:
+    """``out`` = the smoothed geometric median of ``base[rows[j]]``, j < k,
+    after ``iters`` Weiszfeld iterations with smoothing ``nu``
+    (``protocol/aggregation.py``; fedmx_geomed.hip, ``iters + 2`` launches).
+    ``rows_ptr``: device-visible ``int64[k]``, or None for rows 0..k-1.
+    ``workspace``: float64, at least ``geomed_workspace_size(k, P)`` elements
+    on ``base``'s device; allocated when None.  ``weights_out`` / ``dist_out``:
+    float64 ``[k]`` tensors on ``base``'s device, or device-visible addresses,
+    that receive the final weights and the squared distances they came from.
+    With ``state_ptr`` the launches write nothing when the int32 there is
+    negative (no aggregator elected).  Raises ValueError for k, iters or nu out
+    of range; nothing is launched."""
+    if base.dim() != 2 or base.dtype != torch.float32 or not base.is_contiguous():
+        raise ValueError("geomed_aggregate: base must be a contiguous float32 [rows, P] tensor")
+    if base.device.type != "cuda":
+        raise ValueError("geomed_aggregate: base must be on a GPU device")
+    P = int(base.shape[1])
+    if P < 1:
+        raise ValueError("geomed_aggregate: base has no columns")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= GEOMED_MAX_K:
+        raise ValueError(f"geomed_aggregate: k = {k} models (1..{GEOMED_MAX_K} supported)")
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 0 <= iters <= GEOMED_MAX_ITERS:
+        raise ValueError(f"geomed_aggregate: iters = {iters} (an integer in 0..{GEOMED_MAX_ITERS})")
+    if isinstance(nu, bool) or not isinstance(nu, (int, float, np.floating, np.integer)) \
+            or not (float(nu) > 0.0 and math.isfinite(float(nu))):
+        raise ValueError(f"geomed_aggregate: nu = {nu} (finite and > 0)")
+    k, iters, nu = int(k), int(iters), float(nu)
+    if rows_ptr is None and k > base.shape[0]:
+        raise ValueError(f"geomed_aggregate: k = {k} exceeds the stack's {base.shape[0]} rows")
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.numel() != P
+            or not out.is_contiguous() or out.device != base.device):
+        raise ValueError("geomed_aggregate: out must be a contiguous float32 [P] tensor on base's device")
+    need = geomed_workspace_size(k, P)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=base.device)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float64 or workspace.numel() < need
+          or not workspace.is_contiguous() or workspace.device != base.device):
+        raise ValueError(f"geomed_aggregate: workspace must be a contiguous float64 tensor of >= {need} elements "
+                         "on base's device")
+    w_ptr = _geomed_f64_out("weights_out", weights_out, k, base.device)
+    d_ptr = _geomed_f64_out("dist_out", dist_out, k, base.device)
+    _check(lib().fedmx_geomed_agg(base.data_ptr(), rows_ptr or 0, state_ptr, out.data_ptr(), k, P, iters, nu,
+                                  workspace.data_ptr(), w_ptr, d_ptr, _stream(base.device)), "fedmx_geomed_agg")
+    return out
+
+
+def geomed_aggregate_stack(stack: torch.Tensor, iters: int, nu: float, out: Optional[torch.Tensor] = None,
+                           **kw) -> torch.Tensor:
+    """``geomed_aggregate`` over a ``[k, P]`` stack in row order."""
+    st = stack.contiguous()
+    if out is None:
+        out = torch.empty(st.shape[1], dtype=torch.float32, device=st.device)
+    return geomed_aggregate(st, None, int(st.shape[0]), iters, nu, out, **kw)
 
 
 def param_drift(hist: torch.Tensor, new: torch.Tensor, seg: torch.Tensor, to_host: bool = False):

@@ -72,7 +72,7 @@ def plan_fusion(selected: Sequence[int], sim: Dict[int, float] = None, weights: 
     return [(cid, float(x)) for cid, x in zip(selected, w)]
 
 
-UPDATE_TYPES = ("avg", "fedprox", "mse_avg", "fusion_avg", "trimmed_mean", "median", "krum", "multi_krum")
+UPDATE_TYPES = ("avg", "fedprox", "mse_avg", "fusion_avg", "trimmed_mean", "median", "krum", "multi_krum", "geomed")
 
 # Robust rules: a per-coordinate order-statistic selection over the selected
 # models, which no (source, weight) plan expresses.  For every coordinate the
@@ -132,6 +132,64 @@ def krum_counts(update_type: str, k: int, ratio: float = 0.2):
         raise ValueError(f"robust_trim_ratio must be in [0, 0.5), got {ratio}")
     f = min(int(ratio * k), max((k - 3) // 2, 0))
     return f, max(k - f - 2, 0), 1 if update_type == "krum" else k - f
+
+
+# Geometric median (RFA: Pillutla, Kakade, Harchaoui 2019) by smoothed Weiszfeld
+# iterations: a model is down-weighted continuously with its distance from the
+# crowd, no share of poisoned clients is assumed and every honest model keeps
+# its contribution (breakdown point 1/2).  k selected models (rows of P fp32
+# values, selection order; the whole row counts, padding included), T =
+# ``geomed_iters`` in 0..64, nu = ``geomed_nu`` a finite float64 > 0.  All
+# arithmetic is IEEE, one rounding per operation, no contraction.
+#   * block sum of a length-P f64 vector s: zero-extended to nb = ceil(P / 256)
+#     blocks of 256; in block b lane l holds s[256 b + l]; eight folds p_l +=
+#     p_{l+h}, h = 128 .. 1, give q_b = p_0; the sum is ((+0.0 + q_0) + q_1) +
+#     ... + q_{nb-1} in block order;
+#   * lane sum of a length-k f64 vector x: zero-extended to a multiple of 256;
+#     lane l adds x_l + x_{l+256} + ... in that order from +0.0; then the same
+#     eight folds.
+#   1. d_i(z): per coordinate e = fp32(theta_i[c] - z[c]) (one rounding), s_c =
+#      (double)e * (double)e (exact in f64), d_i the block sum of s; d_i(None)
+#      has z = 0, so e = theta_i[c].  A d_i that is NaN or +inf is stored as
+#      +inf, and the row is bad for that step.
+#   2. step -1: d_i = d_i(None), beta_i = 1.0 for a finite d_i, else 0.0 (the
+#      squared norm of a finite fp32 row cannot overflow f64: a row is bad iff
+#      it holds a NaN or an infinity).
+#   3. steps t = 0 .. T: B the lane sum of beta.  B == 0 (every row bad): every
+#      w_i = 0.0, every output coordinate the fp32 NaN 0x7FC00000, and the rule
+#      ends.  Else w_i = beta_i / B (f64); per coordinate acc = +0.0 (f64), and
+#      for i = 0 .. k-1 in selection order with beta_i != 0: acc = acc + (w_i *
+#      (double)theta_i[c]) (the product rounded, then the sum; rows with beta_i
+#      == 0 are not read into the sum); z_t[c] = (float)acc.  t == T stops; else
+#      d_i = d_i(z_t), r_i = sqrt(d_i), beta_i = 1.0 / max(r_i, nu) for a finite
+#      d_i, else 0.0.
+#   4. the aggregate is z_T; weights[k] (f64) the w_i that formed it; dist[k]
+#      (f64) the squared distances d_i those weights came from, +inf for a bad
+#      row  (``Engine.geomed_aggregate``).
+# T = 0 is the mean over the rows that hold no NaN / infinity, accumulated in
+# f64.  Like the other robust rules this is no (source, weight) plan (the
+# weights depend on the models) and it trains plainly.
+GEOMED_TYPES = ("geomed",)
+GEOMED_MAX_ITERS = 64
+
+
+def geomed_check(iters, nu):
+    """``(int(iters), float(nu))`` for ``iters`` an integer in 0..64 and ``nu``
+    a finite float > 0; ValueError otherwise."""
+    import math
+
+    if isinstance(iters, bool) or not hasattr(iters, "__index__"):   # (no floats, no strings)
+        raise ValueError(f"geomed_iters must be an integer in 0..{GEOMED_MAX_ITERS}, got {iters!r}")
+    it = int(iters)
+    if not 0 <= it <= GEOMED_MAX_ITERS:
+        raise ValueError(f"geomed_iters must be an integer in 0..{GEOMED_MAX_ITERS}, got {iters!r}")
+    try:
+        x = float(nu)
+    except (TypeError, ValueError):
+        raise ValueError(f"geomed_nu must be a finite number > 0, got {nu!r}") from None
+    if isinstance(nu, bool) or not (x > 0.0 and math.isfinite(x)):
+        raise ValueError(f"geomed_nu must be a finite number > 0, got {nu!r}")
+    return it, x
 
 
 def make_plan(update_type: str, selected: Sequence[int], aggregator: int, dev_mse: Dict[int, float] = None,

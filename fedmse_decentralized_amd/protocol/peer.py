@@ -30,7 +30,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .aggregation import KRUM_TYPES, ROBUST_TYPES, krum_counts, make_plan, trim_count
+from .aggregation import GEOMED_TYPES, KRUM_TYPES, ROBUST_TYPES, krum_counts, make_plan, trim_count
 from .verification import VerifierState
 
 log = logging.getLogger("fedmx")
@@ -119,6 +119,8 @@ class Peer:
         if fed.update_type in KRUM_TYPES:     # a distance-based choice of whole models
             f, _, m = krum_counts(fed.update_type, len(ids), fed.cfg.robust_trim_ratio)
             return eng.krum_aggregate(stack, f, m)[0]
+        if fed.update_type in GEOMED_TYPES:   # the geometric median: weights that depend on the models
+            return eng.geomed_aggregate(stack, fed.cfg.geomed_iters, fed.cfg.geomed_nu)[0]
         dev_mse = None
         if fed.update_type == "mse_avg":
             saved = eng.store.params[self.row].clone()

@@ -43,6 +43,36 @@ def timeit(fn, reps=20, warm=3):
     return float(np.median(ts)), float(np.min(ts))
 
 
+def aggregation_timings(eng, args) -> dict:
+    """``--aggregation``: the distance-based rules' launches over k models of
+    the benchmark's clients (rows repeated past 10), event-timed over
+    preallocated workspaces: ``krum`` / ``multi_krum`` (three launches) and
+    ``geomed`` at T = 0, 3 and 8 (T + 2 launches) beside the plain weighted sum
+    over the same rows."""
+    from fedmse_decentralized_amd.protocol.aggregation import krum_counts
+
+    dev = eng.device
+    out = {}
+    agg_out = torch.empty(eng.store.params.shape[1], dtype=torch.float32, device=dev)
+    for kk in (5, 40, 256):
+        st = eng.store.params[torch.arange(kk, device=dev) % args.clients].contiguous()
+        # (distinct rows: identical ones would sit at distance 0 of their median)
+        st = st * (1.0 + 0.01 * torch.arange(kk, device=dev, dtype=torch.float32).unsqueeze(1))
+        out[f"weighted_sum_k{kk}_us"] = timeit(lambda: _hip.weighted_sum(st, [1.0 / kk] * kk, out=agg_out),
+                                               reps=args.reps)[0]
+        ws = torch.empty(_hip.krum_workspace_size(kk), dtype=torch.float64, device=dev)
+        for ut in ("krum", "multi_krum"):
+            kf, _, km = krum_counts(ut, kk, 0.2)
+            out[f"{ut}_k{kk}_us"] = timeit(lambda: _hip.krum_aggregate_stack(st, kf, km, out=agg_out, workspace=ws),
+                                           reps=args.reps)[0]
+        gws = torch.empty(_hip.geomed_workspace_size(kk, st.shape[1]), dtype=torch.float64, device=dev)
+        for T in (0, 3, 8):
+            key = f"geomed_k{kk}_us" if T == 3 else f"geomed_T{T}_k{kk}_us"
+            out[key] = timeit(lambda: _hip.geomed_aggregate_stack(st, T, 1e-6, out=agg_out, workspace=gws),
+                              reps=args.reps)[0]
+    return out
+
+
 def detect_timings(eng, clients, args) -> dict:
     """``--detect``: detect_kernel (fedmx_detect.hip) beside auc_kernel on the
     same scores (the benchmark's 10 clients: CEN distances of each test set,
@@ -701,6 +731,8 @@ def main():
     p.add_argument("--detect", action="store_true", help="only the detection-metric timings (detect_kernel beside "
                    "auc_kernel, and ms / round under --metric detection vs classification)")
     p.add_argument("--detect-rounds", type=int, default=200)
+    p.add_argument("--aggregation", action="store_true", help="only the distance-based aggregation rules' timings "
+                   "(krum / multi_krum and geomed at k = 5, 40 and 256 beside the weighted sum over the same rows)")
     p.add_argument("--epochs", type=int, default=5)
     p.add_argument("--clients", type=int, default=10)
     p.add_argument("--train-clients", type=int, default=5)
@@ -721,6 +753,10 @@ def main():
     eng = HipEngine(DEFAULT_DIMS, dev)
     eng.setup([c.train for c in clients], [c.valid for c in clients], [c.test for c in clients],
               [c.test_label for c in clients], init)
+    if args.aggregation:
+        out = aggregation_timings(eng, args)
+        print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
+        return
     if args.detect or args.latent_scorer:
         out = (detect_timings if args.detect else scorer_timings)(eng, clients, args)
         print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
@@ -799,6 +835,11 @@ def main():
             kf, _, km = krum_counts(ut, kk, 0.2)
             out[f"{ut}_k{kk}_us"] = timeit(lambda: _hip.krum_aggregate_stack(st, kf, km, out=agg_out,
                                                                              workspace=ws))[0]
+        # geomed (fedmx_geomed.hip): the T + 2 = 5 launches a round of this rule
+        # pays behind elect_wsum at the default T = 3
+        gws = torch.empty(_hip.geomed_workspace_size(kk, st.shape[1]), dtype=torch.float64, device=dev)
+        out[f"geomed_k{kk}_us"] = timeit(lambda: _hip.geomed_aggregate_stack(st, 3, 1e-6, out=agg_out,
+                                                                             workspace=gws))[0]
     t0 = time.perf_counter()
     for _ in range(20):
         evaluate_clients(eng, allc, "hybrid", "AUC")
