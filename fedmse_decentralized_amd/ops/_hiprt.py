@@ -19,9 +19,10 @@ pinned host memory:
   training tracking) straight into it; the host reads them after the single
   ``hipStreamSynchronize`` that ends each protocol phase.
 
-A ring region is reused only after a stream synchronisation that follows its
-last use (``generation`` bookkeeping), so the host never overwrites bytes a
-queued kernel has yet to read.
+A ring region is reused only after a synchronisation that follows its last use
+(``_Ring`` keeps the span handed out since the last one that covers its stream,
+and drains the device before it would hand out a byte of it again), so the
+host never overwrites bytes a queued kernel has yet to read.
 """
 from __future__ import annotations
 
@@ -277,27 +278,43 @@ class _Ring:
         self._retired = []   # replaced buffers stay alive (host views may still point into them)
         self.stream = stream
         self.off = 0
-        self.wrap_gen = -1   # generation at which the current pass started
+        # The regions a queued kernel may still use are those handed out since
+        # the last synchronisation that covers the stream.  They are contiguous
+        # in ring order: [live_start, off), or once the pass has wrapped,
+        # [live_start, end) and [0, off).  live_start None: nothing in flight.
+        self.live_start: Optional[int] = None
+        self.live_wrapped = False
+        self.live_gen = -1   # SyncClock.of(stream) when live_start was set
+
+    def _drain(self) -> None:
+        device_sync()   # kernels on any stream may still read the ring
+        self.live_start = None
 
     def _alloc(self, nbytes: int) -> int:
         nbytes = (nbytes + 63) & ~63
+        if SyncClock.of(self.stream) > self.live_gen:
+            self.live_start = None   # synchronised since the last allocation
         if nbytes > self.buf.nbytes:
             # grow (rare: very large federations): drain every queued user of
             # the old ring, then replace it with one twice the request
-            device_sync()
+            self._drain()
             self._retired.append(self.buf)
             self.buf = self.buffer_type(2 * nbytes)
             self.off = 0
-            self.wrap_gen = SyncClock.of(self.stream)
-        if self.off + nbytes > self.buf.nbytes:
-            # wrapping: earlier regions may still be read/written by queued kernels
-            # unless a stream synchronisation happened since this pass began
-            if SyncClock.of(self.stream) <= self.wrap_gen:
-                device_sync()   # kernels on any stream may still read the ring
-            self.off = 0
-            self.wrap_gen = SyncClock.of(self.stream)
-        o = self.off
-        self.off += nbytes
+        wrap = self.off + nbytes > self.buf.nbytes
+        o = 0 if wrap else self.off
+        if self.live_start is not None:
+            # the new region must end at or below the oldest one still in
+            # flight once the live span has wrapped (or wraps with this one)
+            if (wrap or self.live_wrapped) and (o + nbytes > self.live_start or (wrap and self.live_wrapped)):
+                self._drain()
+            elif wrap:
+                self.live_wrapped = True
+        if self.live_start is None:
+            self.live_start = o
+            self.live_wrapped = False
+            self.live_gen = SyncClock.of(self.stream)
+        self.off = o + nbytes
         return o
 
 

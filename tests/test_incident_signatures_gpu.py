@@ -13,7 +13,8 @@ Shapes: 115/27/7 (compact forward order), 127/31/15 (identity order), 5/3/2
 and 1/1/1; float32 and float64 rows; both scalers; list lengths bracketing the
 16-position tile, the 64-position pass and the block (R = 64 and 128), with
 incident boundaries inside a tile, at a tile edge and at a block edge, sixteen
-one-row incidents in one tile and one incident over four blocks."""
+one-row incidents in one tile, one incident over four blocks and, at R = 64,
+one over ten (the fold kernel's loop is unrolled by four)."""
 import numpy as np
 import pytest
 import torch
@@ -131,6 +132,8 @@ def test_every_field_matches_the_oracle_on_the_kernels_residuals(dims, dtype, sc
         items = [(m, cuts) for m in lengths(R)]
         items.append((40, tuple(range(16, 33))))   # sixteen one-row incidents in the second tile
         items.append((3 * R + 10, (R - 3,)))       # the second incident lies in blocks 0, 1, 2 and 3
+        if R == 64:
+            items.append((9 * R + 10, (R - 3,)))   # ... in blocks 0 to 9: the fold walks past its four-block unroll
         flags, incs, rows = [], [], []
         for m, c in items:
             f, inc = layout(m, c)
@@ -160,6 +163,8 @@ def test_every_field_matches_the_oracle_on_the_kernels_residuals(dims, dtype, sc
                 assert inc.count == 18 and g.rows[1:17].tolist() == [1] * 16, what
             if m == 3 * R + 10:
                 assert g.rows.tolist() == [R - 3, 2 * R + 13], what
+            if m == 9 * R + 10:
+                assert g.rows.tolist() == [R - 3, 8 * R + 13], what
 
 
 def test_real_incidents_a_subset_and_two_detectors_in_one_call(monkeypatch):
